@@ -14,6 +14,12 @@ Launch (the driver does this):
   python bench.py --gpus 1 --steps K --warmup W
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
+
+A plain run only sets up, warms up, times the K steps and prints the result
+line. --full adds everything else the benchmark measures (at world=1: the
+converged multi-phase Louvain behind the "final modularity" half of the
+metric). --dump-outputs DIR writes what the last timed step computed as
+DIR/<name>.npy so two builds can be compared output for output.
 """
 
 import argparse
@@ -45,6 +51,43 @@ from cuvite_amd.louvain import (LouvainConfig, PhaseState, _modularity,
 from cuvite_amd.parallel import init_from_env  # noqa: E402
 
 
+_DUMP_SAMPLE = 1 << 20  # per-array element cap: 4 fp64 arrays stay at 32 MB
+
+
+def _dump_outputs(out_dir, state, target, q, comm, seed):
+    """Write what the last timed step handed back: the step's modularity,
+    the per-vertex community labels it chose (global ids, exact in fp64),
+    the per-vertex weight into the own community, and the per-community
+    degree/size aggregates it left behind. Arrays longer than _DUMP_SAMPLE
+    are sampled at fixed positions drawn from a CPU generator seeded by
+    --seed and the array length only, so two runs with the same arguments
+    write the same positions."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "" if comm.world == 1 else f"_rank{comm.rank}"
+    n = target.numel()
+    if n > _DUMP_SAMPLE:
+        gen = torch.Generator().manual_seed(seed * 1000003 + n)
+        pos = torch.randint(0, n, (_DUMP_SAMPLE,), generator=gen)
+        pos = pos.sort().values.to(target.device)
+    else:
+        pos = None
+    arrays = {
+        "communities": target,
+        "cluster_weight": state.cluster_weight,
+        "community_degree": state.local_degree,
+        "community_size": state.local_size,
+    }
+    for name, t in arrays.items():
+        if pos is not None:
+            t = t[pos]
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"),
+                t.to(torch.float64).cpu().numpy())
+    np.save(os.path.join(out_dir, f"modularity{sfx}.npy"),
+            np.asarray([q], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -56,11 +99,21 @@ def main():
     ap.add_argument("--dtype", choices=["fp64", "fp32"], default="fp64")
     ap.add_argument("--backend", default="auto",
                     help="auto|hip|torch (torch = eager fallback, CPU test only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run everything beyond "
+                         "the headline figure (at world=1: the converged "
+                         "multi-phase Louvain, reported under config)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/*.npy")
     ap.add_argument("--converge", action="store_true",
                     help="also run a full multi-phase Louvain to convergence "
-                         "AFTER the timed region and report final modularity")
+                         "AFTER the timed region and report final modularity "
+                         "(what --full turns on at world=1; this forces it "
+                         "at any world size)")
     ap.add_argument("--no-converge", action="store_true")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     comm = init_from_env()
     device = comm.device
@@ -135,12 +188,19 @@ def main():
 
     teps = ne_global * args.steps / elapsed
 
+    if args.dump_outputs:
+        # step() leaves the labels it chose in state.curr_comm
+        _dump_outputs(args.dump_outputs, state, state.curr_comm, q, comm,
+                      args.seed)
+        _p(f"outputs written to {args.dump_outputs}")
+
     # Converged full run (outside the timed region): evidences the "final
-    # modularity" half of the BASELINE metric. Default on at world=1 (the
-    # driver's BENCH run); opt-in for multi-GPU (--converge) so the SCALE
-    # sweep stays a pure per-iteration measurement.
+    # modularity" half of the BASELINE metric. Only with --full, where it is
+    # on at world=1; opt-in for multi-GPU (--converge) so the SCALE sweep
+    # stays a pure per-iteration measurement.
     conv = None
-    do_conv = args.converge or (comm.world == 1 and not args.no_converge
+    do_conv = args.converge or (args.full and comm.world == 1
+                                and not args.no_converge
                                 and os.environ.get("CUVITE_NO_CONVERGE") != "1")
     if do_conv:
         from cuvite_amd.louvain import louvain
