@@ -46,6 +46,46 @@ def _hash_scalar(a: int, seed: int) -> int:
     return int(_hash(torch.tensor([a], dtype=torch.int64), seed)[0])
 
 
+def _minmax_torch(rowptr, tails_dense, gid_all, uncolored_all, colors, base,
+                  seeds):
+    """Torch path of one coloring round: per-vertex strict min / max of each
+    hash over COMPETING neighbors (uncolored at round start, not self), one
+    (mn, mx) pair of int64 [nv] per seed; vertices without a competitor (or
+    already colored) keep the sentinels 1<<33 / -1. The coloring_minmax HIP
+    kernel computes the same thing and is tested against this function."""
+    dev = rowptr.device
+    nv = rowptr.numel() - 1
+    ne = tails_dense.numel()
+    # edges are processed in chunks: boolean compaction over a >INT_MAX edge
+    # array overflows torch's internal indexing (hit at R-MAT s26), and
+    # chunking also avoids materializing 17 GB seg/tail_gid arrays
+    CH = 1 << 28
+    mns = [torch.full((nv,), 1 << 33, dtype=torch.int64, device=dev)
+           for _ in seeds]
+    mxs = [torch.full((nv,), -1, dtype=torch.int64, device=dev)
+           for _ in seeds]
+    for c0 in range(0, ne, CH):
+        c1 = min(c0 + CH, ne)
+        eidx = torch.arange(c0, c1, device=dev)
+        seg_c = torch.searchsorted(rowptr, eidx, right=True) - 1
+        del eidx
+        tails_c = tails_dense[c0:c1].to(torch.int64)
+        tail_gid_c = gid_all[tails_c]
+        cand = (tail_gid_c != (seg_c + base)) \
+            & uncolored_all[tails_c] & (colors[seg_c] < 0)
+        del tails_c
+        e_seg = seg_c[cand]
+        e_tail_gid = tail_gid_c[cand]
+        del seg_c, tail_gid_c, cand
+        if not e_seg.numel():
+            continue
+        for t, sd in enumerate(seeds):
+            jh = _hash(e_tail_gid, sd)
+            mns[t].scatter_reduce_(0, e_seg, jh, reduce="amin")
+            mxs[t].scatter_reduce_(0, e_seg, jh, reduce="amax")
+    return mns, mxs
+
+
 def distance1_coloring(dg: DistGraph, comm: Comm, n_hash: int = 4,
                        halo=None) -> Tuple[torch.Tensor, int]:
     """Returns (colors int64 [nv] in [0, num_colors), num_colors).
@@ -59,13 +99,8 @@ def distance1_coloring(dg: DistGraph, comm: Comm, n_hash: int = 4,
     if halo is None:
         halo = build_halo(dg, comm)
     rowptr = dg.g.rowptr
-    ne = dg.g.ne
     gid_all = torch.cat([torch.arange(base, dg.bound, device=dev), halo.ghosts])
     tnv = dg.nv_global
-    # edges are processed in chunks: boolean compaction over a >INT_MAX edge
-    # array overflows torch's internal indexing (hit at R-MAT s26), and
-    # chunking also avoids materializing 17 GB seg/tail_gid arrays
-    CH = 1 << 28
 
     colors = torch.full((nv,), -1, dtype=torch.int64, device=dev)
     seed = 1012
@@ -95,31 +130,9 @@ def distance1_coloring(dg: DistGraph, comm: Comm, n_hash: int = 4,
             mns = [mn2[:, t] for t in range(n_hash)]
             mxs = [mx2[:, t] for t in range(n_hash)]
         else:
-            # chunked torch path (boolean compaction over >INT_MAX edges
-            # overflows torch's internal indexing, hence CH slices)
-            mns = [torch.full((nv,), 1 << 33, dtype=torch.int64, device=dev)
-                   for _ in range(n_hash)]
-            mxs = [torch.full((nv,), -1, dtype=torch.int64, device=dev)
-                   for _ in range(n_hash)]
-            for c0 in range(0, ne, CH):
-                c1 = min(c0 + CH, ne)
-                eidx = torch.arange(c0, c1, device=dev)
-                seg_c = torch.searchsorted(rowptr, eidx, right=True) - 1
-                del eidx
-                tails_c = halo.tails_dense[c0:c1].to(torch.int64)
-                tail_gid_c = gid_all[tails_c]
-                cand = (tail_gid_c != (seg_c + base)) \
-                    & uncolored_all[tails_c] & (colors[seg_c] < 0)
-                del tails_c
-                e_seg = seg_c[cand]
-                e_tail_gid = tail_gid_c[cand]
-                del seg_c, tail_gid_c, cand
-                if not e_seg.numel():
-                    continue
-                for t in range(n_hash):
-                    jh = _hash(e_tail_gid, seed + 1043 * t)
-                    mns[t].scatter_reduce_(0, e_seg, jh, reduce="amin")
-                    mxs[t].scatter_reduce_(0, e_seg, jh, reduce="amax")
+            mns, mxs = _minmax_torch(
+                rowptr, halo.tails_dense, gid_all, uncolored_all, colors,
+                base, [seed + 1043 * t for t in range(n_hash)])
 
         avail = torch.zeros(nv, 2 * n_hash, dtype=torch.bool, device=dev)
         vgid = torch.arange(base, dg.bound, device=dev)

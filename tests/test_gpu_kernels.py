@@ -95,11 +95,12 @@ def test_local_move_fp32():
 
 
 def test_degree_class_coverage():
-    """Graph with vertices in every degree class including hubs (>4096)."""
+    """Graph with vertices in every degree class including hubs (deg above
+    the hub cut, 6144 by default)."""
     from cuvite_amd import ops
     dev = torch.device("cuda:0")
-    # star graph: hub 0 with 6000 spokes + chain among low vertices
-    n_sp = 6000
+    # star graph: hub 0 with 7000 spokes + chain among low vertices
+    n_sp = 7000
     nv = n_sp + 1
     src = [0] * n_sp + list(range(1, nv))
     dst = list(range(1, nv)) + [0] * n_sp
