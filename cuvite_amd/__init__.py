@@ -12,6 +12,8 @@ __version__ = "0.1.0"
 
 from .graph import Graph, DistGraph, Partition
 from .louvain import louvain, LouvainConfig, LouvainResult
+from .quality import (PartitionQuality, intra_weight_torch,
+                      partition_quality)
 
 __all__ = [
     "Graph",
@@ -20,5 +22,8 @@ __all__ = [
     "louvain",
     "LouvainConfig",
     "LouvainResult",
+    "PartitionQuality",
+    "partition_quality",
+    "intra_weight_torch",
     "__version__",
 ]

@@ -29,6 +29,7 @@ from .io import (load_dist_graph, load_ground_truth, write_communities,
                  write_dist_graph)
 from .louvain import LouvainConfig, louvain
 from .parallel import Comm, init_from_env
+from .quality import partition_quality
 from .utils.stats import print_dist_stats
 
 
@@ -106,6 +107,17 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--unit-weights", action="store_true",
                     help="force all edge weights to 1.0 for file inputs "
                     "(ref SET_EDGE_WEIGHTS_TO_ONE, distgraph.cpp:200-202)")
+    ap.add_argument("--score-communities", metavar="FILE", default="",
+                    help="print the exact modularity of the partition in "
+                    "FILE (a -o dump or a ground-truth file; -z applies) on "
+                    "this graph and exit without clustering")
+    ap.add_argument("--init-communities", metavar="FILE", default="",
+                    help="warm start: begin clustering from the partition "
+                    "in FILE instead of singletons (-z applies)")
+    ap.add_argument("--exact-modularity", action="store_true",
+                    help="after the run, print the exact modularity of the "
+                    "returned partition (\"Final modularity\" is the "
+                    "convergence estimate)")
     ap.add_argument("--stats", action="store_true",
                     help="print the graph distribution table "
                     "(ref printStats, distgraph.hpp:100-149)")
@@ -170,6 +182,24 @@ def _ingest(args, comm: Comm) -> DistGraph:
                            weight_dtype=wdtype)
 
 
+def _load_partition_slice(path: str, args, dg: DistGraph) -> torch.Tensor:
+    """This rank's slice of the partition in `path`, in INPUT vertex order.
+    Every rank reads the whole file, so every rank takes the same exit on a
+    bad one. Label values are compacted to [0, k): ground-truth files with
+    ids >= N or with gaps then satisfy the [0, nv_global) label contract."""
+    import numpy as np
+    try:
+        lab = load_ground_truth(path, zero_based=not args.one_based)
+    except FileNotFoundError:
+        sys.exit(f"Error opening community file: {path}")
+    if lab.numel() != dg.nv_global:
+        sys.exit(f"Community file {path} has {lab.numel()} entries; the "
+                 f"graph has {dg.nv_global} vertices")
+    _, inv = np.unique(lab.numpy(), return_inverse=True)
+    inv = torch.from_numpy(inv.astype(np.int64).reshape(-1))
+    return inv[dg.base:dg.bound].to(dg.g.device)
+
+
 def write_dist_graph_collect(path: str, dg: DistGraph, comm: Comm):
     """Root-gathers shards and writes one Vite binary (ref writeGraph,
     distgraph.cpp:936-1014; cold path, host-side)."""
@@ -218,6 +248,20 @@ def main(argv=None) -> int:
     if args.just_process:
         return 0
 
+    if args.score_communities:
+        pq = partition_quality(
+            dg, _load_partition_slice(args.score_communities, args, dg),
+            comm, backend=args.backend)
+        if comm.rank == 0:
+            print(f"Partition {args.score_communities}: "
+                  f"modularity={pq.modularity:.15g} "
+                  f"communities={pq.num_communities} "
+                  f"coverage={pq.coverage:.15g}")
+        return 0
+    init_labels = None
+    if args.init_communities:
+        init_labels = _load_partition_slice(args.init_communities, args, dg)
+
     vo_inv = None     # new local pos -> old local pos (inverse applied later)
     vo_gmap = None    # old gid -> new gid
     if args.vertex_order == "degree":
@@ -242,9 +286,19 @@ def main(argv=None) -> int:
     if args.max_phases:
         cfg.max_phases = args.max_phases
 
+    if init_labels is not None:
+        if vo_inv is not None:
+            # relabelled local position p holds input-order vertex
+            # vo_order[p]; community ids are opaque, so values stay
+            init_labels = init_labels[vo_order]
+        pq = partition_quality(dg, init_labels, comm, backend=args.backend)
+        if comm.rank == 0:
+            print(f"Initial partition: modularity={pq.modularity:.15g} "
+                  f"communities={pq.num_communities}")
+
     comm.barrier()
     t0 = time.perf_counter()
-    res = louvain(dg, comm, cfg)
+    res = louvain(dg, comm, cfg, init_labels=init_labels)
     comm.barrier()
     t_total = time.perf_counter() - t0
 
@@ -271,6 +325,15 @@ def main(argv=None) -> int:
                   f"device {hbm_gb:.2f} GB")
         else:
             print(f"Peak memory: host rss {rss_mb:.0f} MB")
+
+    if args.exact_modularity:
+        # res.communities labels the graph that was clustered (after
+        # --vertex-order degree the relabelled, isomorphic one)
+        pq = partition_quality(dg, res.communities, comm,
+                               backend=args.backend)
+        if comm.rank == 0:
+            print(f"Exact modularity: {pq.modularity:.15g} "
+                  f"({pq.num_communities} communities)")
 
     builtin_truth = getattr(args, "_lfr_truth", None)
     if args.output or args.ground_truth or builtin_truth is not None:

@@ -30,6 +30,7 @@ from .halo import (build_halo, exchange_ghost_labels, fetch_comm_info_lists,
 from .local_move import MoveInputs, local_move_torch, modularity_parts
 from .ops import scatter_add_
 from .parallel import Comm
+from .quality import community_aggregates, validate_labels
 from .utils.timers import Timers
 
 TERMINATION_PHASE_COUNT = 200   # ref utils.hpp:17-19
@@ -56,7 +57,8 @@ class LouvainConfig:
 
 @dataclass
 class LouvainResult:
-    modularity: float
+    modularity: float           # convergence estimate, NOT the exact Q of
+    #   `communities` (see quality.partition_quality for that)
     communities: torch.Tensor   # final community id per ORIGINAL local vertex
     phases: int
     total_iters: int
@@ -99,8 +101,11 @@ def _pick_move_fn(cfg: LouvainConfig, device: torch.device):
 class PhaseState:
     """Mutable per-phase state for one rank (all tensors on dg's device)."""
 
-    def __init__(self, dg: DistGraph, comm: Comm, halo=None):
+    def __init__(self, dg: DistGraph, comm: Comm, halo=None,
+                 init_labels: Optional[torch.Tensor] = None):
         dev = dg.g.device
+        if init_labels is not None:
+            validate_labels(dg, comm, init_labels)  # before any collective
         self.dg = dg
         self.comm = comm
         self.halo = halo if halo is not None else build_halo(dg, comm)
@@ -114,6 +119,14 @@ class PhaseState:
         arange = torch.arange(dg.base, dg.bound, device=dev)
         self.curr_comm = arange.clone()
         self.past_comm = arange.clone()
+        if init_labels is not None:
+            # warm start: arbitrary global labels; aggregates rebuilt from
+            # them (everything downstream already copes: densify interns
+            # the remote ids on its first call)
+            self.curr_comm = init_labels.to(dev).clone()
+            self.past_comm = self.curr_comm.clone()
+            self.local_size, self.local_degree = community_aggregates(
+                dg, comm, self.halo, self.curr_comm, self.v_degree)
         # constant = 1/(2m) (ref distCalcConstantForSecondTerm; guard the
         # edgeless-graph case the reference would divide by zero on)
         tw = float(self.v_degree.to(torch.float64).sum())
@@ -340,12 +353,13 @@ def _et_update(state: PhaseState, cfg: LouvainConfig, target: torch.Tensor,
 def run_phase(dg: DistGraph, comm: Comm, cfg: LouvainConfig,
               lower: float, threshold: float,
               colors: Optional[torch.Tensor] = None,
-              num_colors: int = 0, halo=None):
+              num_colors: int = 0, halo=None,
+              init_labels: Optional[torch.Tensor] = None):
     """One Louvain phase (local moving to convergence). Returns
     (prev_mod, cvect global labels [nv], iters).
     Ref: distLouvainMethod (louvain.cpp:425-588) and the coloring/ordering
     variants (louvain.cpp:756-2101)."""
-    state = PhaseState(dg, comm, halo=halo)
+    state = PhaseState(dg, comm, halo=halo, init_labels=init_labels)
     move_fn = _pick_move_fn(cfg, dg.g.device)
     state.use_hip = (dg.g.device.type == "cuda"
                      and cfg.backend in ("auto", "hip"))
@@ -529,12 +543,16 @@ def _modularity(state: PhaseState) -> float:
 
 def louvain(dg: DistGraph, comm: Optional[Comm] = None,
             cfg: Optional[LouvainConfig] = None,
-            halo=None) -> LouvainResult:
+            halo=None,
+            init_labels: Optional[torch.Tensor] = None) -> LouvainResult:
     """Full multi-phase Louvain (ref main.cpp:218-495). Returns the final
     community id per ORIGINAL local vertex (contiguous global ids) and the
     final modularity. `halo`: optional prebuilt HaloContext for the INPUT
     graph (phase 0) — callers that already built one (bench.py's timed
-    region) pass it to avoid a duplicate ghost structure (17 GB at s27)."""
+    region) pass it to avoid a duplicate ghost structure (17 GB at s27).
+    `init_labels`: warm start — int64 [nv] global community ids in
+    [0, nv_global) for this rank's vertices; phase 0 starts from them
+    instead of singletons (ValueError on every rank if any slice is bad)."""
     from .coarsen import coarsen, remap_labels
     from .coloring import distance1_coloring
 
@@ -576,7 +594,8 @@ def louvain(dg: DistGraph, comm: Optional[Comm] = None,
         halo = None  # phase-0 halo ownership moves to run_phase/coarsen
         curr_mod, cvect, iters, phase_halo = run_phase(
             level, comm, cfg, curr_mod, threshold,
-            colors=colors, num_colors=num_colors, halo=pre_halo)
+            colors=colors, num_colors=num_colors, halo=pre_halo,
+            init_labels=init_labels if phase == 0 else None)
         pre_halo = None
         t_cluster = time.perf_counter() - t0
         times["clustering"] += t_cluster

@@ -398,6 +398,22 @@ def modularity_parts(cluster_weight: torch.Tensor,
     return ext.modularity_parts(cluster_weight, local_comm_degree)
 
 
+def intra_weight(rowptr: torch.Tensor, tails_dense: torch.Tensor,
+                 weights: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    """out[v] = sum of w[e] over row v's edges whose tail carries v's label,
+    for ARBITRARY labels (int32 dense or int64 global ids, [nv + ng], local
+    vertices first): the `cw` that local_move returns, self-loops and
+    parallel edges included, without the hash-table pass. Edge-balanced
+    HIP kernel on the current stream; output has the weights' dtype."""
+    return _require().intra_weight(rowptr, tails_dense, weights, labels)
+
+
+def intra_weight_span() -> int:
+    """Edges per wave span of the intra_weight kernel (rows cut by a span
+    boundary take the atomic path; tests build their shapes around it)."""
+    return int(_require().intra_weight_span())
+
+
 def scatter_add_(out: torch.Tensor, idx: torch.Tensor,
                  val: torch.Tensor) -> torch.Tensor:
     """out[idx[i]] += val[i]. On GPU float tensors this MUST go through the

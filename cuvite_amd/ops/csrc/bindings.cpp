@@ -70,6 +70,10 @@ void launch_coloring_minmax(const int64_t*, const int32_t*, const int64_t*,
                             const bool*, const int64_t*, int64_t, int64_t,
                             const int64_t*, int, int64_t*, int64_t*,
                             hipStream_t);
+template <typename W, typename L>
+void launch_intra_weight(const int64_t*, const int32_t*, const W*, const L*,
+                         int64_t, int64_t, int64_t, W*, hipStream_t);
+int intra_weight_span();
 
 }  // namespace cuvite
 
@@ -437,6 +441,43 @@ at::Tensor row_sum(at::Tensor rowptr, at::Tensor weights) {
   return out;
 }
 
+// Per-vertex weight into the vertex's own community for arbitrary labels
+// (see intra_weight_kernel). labels: int32 or int64, [nv + ng].
+at::Tensor intra_weight(at::Tensor rowptr, at::Tensor tails,
+                        at::Tensor weights, at::Tensor labels) {
+  CHECK_DEV(rowptr); CHECK_CONT(rowptr);
+  CHECK_DEV(tails); CHECK_CONT(tails);
+  CHECK_DEV(weights); CHECK_CONT(weights);
+  CHECK_DEV(labels); CHECK_CONT(labels);
+  TORCH_CHECK(rowptr.scalar_type() == at::kLong, "rowptr must be int64");
+  TORCH_CHECK(rowptr.numel() >= 1, "rowptr must have nv + 1 entries");
+  TORCH_CHECK(tails.scalar_type() == at::kInt, "tails must be int32");
+  TORCH_CHECK(labels.scalar_type() == at::kInt ||
+              labels.scalar_type() == at::kLong,
+              "labels must be int32 or int64");
+  TORCH_CHECK(tails.numel() == weights.numel(), "tails/weights mismatch");
+  const int64_t nv = rowptr.numel() - 1;
+  TORCH_CHECK(nv < (int64_t)INT32_MAX, "nv exceeds the int32 dense id range");
+  TORCH_CHECK(labels.numel() >= nv, "labels must cover all local vertices");
+  auto out = at::zeros({nv}, weights.options());
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  AT_DISPATCH_FLOATING_TYPES(weights.scalar_type(), "intra_weight", [&] {
+    using W = scalar_t;
+    if (labels.scalar_type() == at::kInt)
+      cuvite::launch_intra_weight<W, int32_t>(
+          rowptr.data_ptr<int64_t>(), tails.data_ptr<int32_t>(),
+          weights.data_ptr<W>(), labels.data_ptr<int32_t>(), nv,
+          tails.numel(), labels.numel(), out.data_ptr<W>(), stream);
+    else
+      cuvite::launch_intra_weight<W, int64_t>(
+          rowptr.data_ptr<int64_t>(), tails.data_ptr<int32_t>(),
+          weights.data_ptr<W>(), labels.data_ptr<int64_t>(), nv,
+          tails.numel(), labels.numel(), out.data_ptr<W>(), stream);
+  });
+  C10_HIP_CHECK(hipGetLastError());
+  return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -458,6 +499,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "per-vertex multi-hash min/max over competing neighbors (HIP)");
   m.def("recount_", &recount_,
         "fresh community size/degree recount from labels (HIP)");
+  m.def("intra_weight", &intra_weight,
+        "per-vertex weight into the own community, edge-balanced (HIP)");
+  m.def("intra_weight_span", &cuvite::intra_weight_span,
+        "edges per wave span of the intra_weight kernel");
   m.def("hub_moves", &hub_moves,
         "full device-side hub move: segsort + reduce_by_key + argmax");
 }

@@ -560,6 +560,124 @@ __global__ __launch_bounds__(BLOCK) void row_sum_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// intra_weight: out[v] = sum over row v of w[e] * [labels[tails[e]] ==
+// labels[v]] for ARBITRARY labels (partition scoring, warm start) — the `cw`
+// the move kernels produce, without the hash-table pass.
+//
+// Edge-balanced, not row-balanced: R-MAT rows range from < 16 edges to
+// millions, so a wave-per-row layout (row_sum_kernel) leaves one wave
+// walking a hub while the rest idle. Each wave owns a span of IW_SPAN
+// consecutive edges and reads them lane-strided (coalesced tails/weights,
+// one random label gather per edge). The span's first row comes from a
+// binary search in rowptr and its last row from a gallop out of the first;
+// every lane then finds the row of its own edge by a binary search inside
+// that (wave-uniform, L1-resident) row range. Rows are contiguous runs of
+// lanes, so a segmented shuffle scan sums them; a run that continues into
+// the next 64-edge chunk is carried in registers. A row wholly inside the
+// span gets one plain store; a row cut by a span boundary is added with a
+// native float atomic into the zero-initialised output (at most two
+// atomics per span). Sums inside a span are fp64 whatever the weight type.
+// ---------------------------------------------------------------------------
+
+constexpr int IW_SPAN = 4096;  // edges per wave: 64 chunks amortise the
+                               // ~30 dependent loads of the row searches
+constexpr int IW_PIPE = 4;     // chunks of loads in flight (as in
+                               // insert_edges_pipelined)
+
+// Largest r in [lo, hi] with rowptr[r] <= e (skips zero-degree rows).
+DEV_INLINE int64_t row_of_edge(const int64_t* __restrict__ rowptr, int64_t lo,
+                               int64_t hi, int64_t e) {
+  while (lo < hi) {
+    const int64_t m = (lo + hi + 1) >> 1;
+    if (rowptr[m] <= e) lo = m; else hi = m - 1;
+  }
+  return lo;
+}
+
+template <typename W, typename L, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void intra_weight_kernel(
+    const int64_t* __restrict__ rowptr, const int32_t* __restrict__ tails,
+    const W* __restrict__ weights, const L* __restrict__ labels, int64_t nv,
+    int64_t ne, int64_t nl, W* __restrict__ out) {
+  constexpr int WAVES = BLOCK / 64;
+  const int lane = threadIdx.x % 64;
+  const int64_t nspan = (ne + IW_SPAN - 1) / IW_SPAN;
+  // wave-strided over spans: grid stays under the work-item cap
+  const int64_t sstride = (int64_t)gridDim.x * WAVES;
+  for (int64_t s = (int64_t)blockIdx.x * WAVES + threadIdx.x / 64; s < nspan;
+       s += sstride) {
+    const int64_t s0 = s * IW_SPAN;
+    const int64_t s1 = (s0 + IW_SPAN < ne) ? s0 + IW_SPAN : ne;
+    // wave-uniform row range of the span
+    int64_t rlo = row_of_edge(rowptr, 0, nv - 1, s0);
+    int64_t rhi = rlo, step = 1;
+    while (rhi + step < nv && rowptr[rhi + step] < s1) {
+      rhi += step;
+      step <<= 1;
+    }
+    rhi = (rhi + step - 1 < nv - 1) ? rhi + step - 1 : nv - 1;
+
+    double carry_val = 0.0;
+    int32_t carry_row = -1;  // row whose run continues from the last chunk
+    for (int64_t c = s0; c < s1; c += (int64_t)IW_PIPE * 64) {
+      int32_t t[IW_PIPE];
+      W w[IW_PIPE];
+#pragma unroll
+      for (int k = 0; k < IW_PIPE; k++) {
+        const int64_t e = c + k * 64 + lane;
+        const bool ok = e < s1;
+        t[k] = ok ? tails[e] : 0;
+        w[k] = ok ? weights[e] : (W)0;
+      }
+      L lt[IW_PIPE];
+      bool inb[IW_PIPE];
+#pragma unroll
+      for (int k = 0; k < IW_PIPE; k++) {
+        // memory-safety guard: a tail outside the label array matches nothing
+        inb[k] = (uint64_t)(int64_t)t[k] < (uint64_t)nl;
+        lt[k] = inb[k] ? labels[t[k]] : (L)0;
+      }
+#pragma unroll
+      for (int k = 0; k < IW_PIPE; k++) {
+        const int64_t cb = c + k * 64;
+        if (cb >= s1) break;  // wave-uniform
+        const int64_t e = cb + lane;
+        const bool ok = e < s1;
+        int32_t row = -2;  // lanes past the span: one inert run
+        int64_t rend = 0;
+        double val = 0.0;
+        if (ok) {
+          row = (int32_t)row_of_edge(rowptr, rlo, rhi, e);
+          rend = rowptr[(int64_t)row + 1];
+          if (inb[k] && lt[k] == labels[row]) val = (double)w[k];
+        }
+        if (lane == 0 && row == carry_row) val += carry_val;
+        // segmented inclusive scan: equal rows are contiguous lanes
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+          const double pv = __shfl_up(val, off, 64);
+          const int32_t pr = __shfl_up(row, off, 64);
+          if (lane >= off && pr == row) val += pv;
+        }
+        const bool tail = ok && (e == rend - 1 || e == s1 - 1);
+        if (tail) {
+          if (rowptr[row] >= s0 && rend <= s1)
+            out[row] = (W)val;
+          else
+            unsafeAtomicAdd(&out[row], (W)val);
+        }
+        // only a full chunk can end inside a run (a partial chunk ends the
+        // span, and its last edge is a tail)
+        carry_val = __shfl(val, 63, 64);
+        carry_row = __shfl(tail ? -1 : row, 63, 64);
+        const int32_t last_row = __shfl(row, 63, 64);
+        if (last_row >= 0) rlo = last_row;
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Hub candidate generation via rocPRIM (CUVITE_HUB_SEGSORT experiment):
 // per-hub segmented radix sort of the community keys (only ceil(log2 C) bits)
 // + reduce_by_key for the (hub, community) weight sums. The torch path sorts
@@ -961,6 +1079,30 @@ template void launch_row_sum<float>(const int64_t*, const float*, int64_t,
                                     float*, hipStream_t);
 template void launch_row_sum<double>(const int64_t*, const double*, int64_t,
                                      double*, hipStream_t);
+
+// `out` must be zero-initialised by the caller (rows cut by a span boundary
+// are accumulated with atomics; edgeless rows are never written).
+template <typename W, typename L>
+void launch_intra_weight(const int64_t* rowptr, const int32_t* tails,
+                         const W* weights, const L* labels, int64_t nv,
+                         int64_t ne, int64_t nl, W* out, hipStream_t stream) {
+  if (nv == 0 || ne == 0) return;
+  constexpr int BLOCK = 256;
+  const int64_t nspan = (ne + IW_SPAN - 1) / IW_SPAN;
+  hipLaunchKernelGGL((intra_weight_kernel<W, L, BLOCK>),
+                     dim3(grid_for(nspan * 64, BLOCK)), dim3(BLOCK), 0, stream,
+                     rowptr, tails, weights, labels, nv, ne, nl, out);
+}
+#define INSTANTIATE_IW(W, L)                                                  \
+  template void launch_intra_weight<W, L>(const int64_t*, const int32_t*,    \
+                                          const W*, const L*, int64_t,       \
+                                          int64_t, int64_t, W*, hipStream_t);
+INSTANTIATE_IW(float, int32_t)
+INSTANTIATE_IW(float, int64_t)
+INSTANTIATE_IW(double, int32_t)
+INSTANTIATE_IW(double, int64_t)
+
+int intra_weight_span() { return IW_SPAN; }
 
 // rocPRIM wrappers (two-phase: bytes query with temp==nullptr, then run).
 template <typename W>
