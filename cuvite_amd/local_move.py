@@ -28,6 +28,7 @@ for tie-breaks and the singleton guard).
 from __future__ import annotations
 
 from dataclasses import dataclass
+from typing import Optional
 
 import torch
 
@@ -45,6 +46,11 @@ class MoveInputs:
     comm_degree: torch.Tensor  # W [nc]
     comm_gid: torch.Tensor     # int64 [nc]  dense comm id -> global comm id
     constant: float            # 1 / (2m)
+    # Optional promise about comm_gid: comm_gid[i] == local_gid_base + i for
+    # i < nv (the locally owned communities). The HIP kernels then compute
+    # those ids instead of gathering them; local_move_torch and
+    # local_move_pydict ignore it.
+    local_gid_base: Optional[int] = None
 
     @property
     def nv(self) -> int:

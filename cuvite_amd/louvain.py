@@ -18,6 +18,7 @@ PhaseState.densify).
 
 from __future__ import annotations
 
+import os
 import time
 from dataclasses import dataclass, field
 from typing import List, Optional
@@ -141,6 +142,47 @@ class PhaseState:
         self._parts_dev: Optional[torch.Tensor] = None
         self._runiv: Optional[torch.Tensor] = None
         self._prev_labels: Optional[torch.Tensor] = None
+        # fused-step buffers (see fused_next), built on first use
+        self._agg_spare = None
+        self._iso_size: Optional[torch.Tensor] = None
+
+    def fused_step_ok(self, cfg: "LouvainConfig", move_fn) -> bool:
+        """Whether the plain sweep may let the move kernels account the new
+        community aggregates themselves instead of calling apply_moves:
+        one rank, HIP backend, no early termination, rocPRIM hub path, plain
+        schedule. CUVITE_FUSED_AGG=0 forces the unfused path."""
+        if (self.comm.world != 1 or not getattr(self, "use_hip", False)
+                or cfg.early_term
+                or os.environ.get("CUVITE_FUSED_AGG", "1") in ("0", "off")):
+            return False
+        from . import ops
+        return move_fn is ops.local_move and ops.fused_aggregates_supported()
+
+    def fused_next(self):
+        """The spare (size, degree) pair for a fused step, pre-loaded with
+        what the move kernels never visit: vertices without edges keep their
+        label for the whole phase and have degree 0, so their share of every
+        community's size is a phase constant (iso_size, also right under a
+        warm start) and their share of the degrees is zero. Runs on the
+        current stream; the caller hands the pair to the move and rebinds
+        local_size / local_degree to it afterwards (adopt_next)."""
+        if self._iso_size is None:
+            rowptr = self.dg.g.rowptr
+            iso = (rowptr[1:] == rowptr[:-1]).nonzero(as_tuple=True)[0]
+            self._iso_size = torch.bincount(
+                self.curr_comm[iso] - self.dg.base, minlength=self.dg.nv)
+            self._agg_spare = (torch.empty_like(self.local_size),
+                               torch.empty_like(self.local_degree))
+        nsize, ndegree = self._agg_spare
+        nsize.copy_(self._iso_size)
+        ndegree.zero_()
+        return nsize, ndegree
+
+    def adopt_next(self, nsize: torch.Tensor, ndegree: torch.Tensor):
+        """Make the pair a fused step filled the current aggregates; the
+        pair the kernels read becomes the spare."""
+        self._agg_spare = (self.local_size, self.local_degree)
+        self.local_size, self.local_degree = nsize, ndegree
 
     def _local_gids(self) -> torch.Tensor:
         if self._lgids is None:
@@ -420,7 +462,17 @@ def _one_sweep(state: PhaseState, cfg: LouvainConfig, move_fn,
         dense, remote_gids, c_size, c_degree, c_gid = state.densify(ghost_comm)
         inp = MoveInputs(state.dg.g.rowptr, state.halo.tails_dense,
                          state.dg.g.weights, dense, state.v_degree,
-                         c_size, c_degree, c_gid, state.constant)
+                         c_size, c_degree, c_gid, state.constant,
+                         local_gid_base=state.dg.base)
+        if state.fused_step_ok(cfg, move_fn):
+            # the kernels that store the targets also build the new
+            # aggregates in the spare pair (c_size / c_degree, the pair they
+            # read, stays untouched); no recount pass afterwards
+            nsize, ndegree = state.fused_next()
+            tgt_dense, cw = move_fn(inp, next_size=nsize, next_degree=ndegree)
+            state.adopt_next(nsize, ndegree)
+            state.cluster_weight = cw
+            return _dense_to_gid(state, tgt_dense, remote_gids)
         tgt_dense, cw = move_fn(inp)
         target = _dense_to_gid(state, tgt_dense, remote_gids)
         if cfg.early_term:
@@ -447,7 +499,8 @@ def _one_sweep(state: PhaseState, cfg: LouvainConfig, move_fn,
         state.curr_comm = saved
         inp = MoveInputs(state.dg.g.rowptr, state.halo.tails_dense,
                          state.dg.g.weights, dense, state.v_degree,
-                         c_size, c_degree, c_gid, state.constant)
+                         c_size, c_degree, c_gid, state.constant,
+                         local_gid_base=state.dg.base)
         tgt_dense, cw = move_fn(inp)
         tgt = _dense_to_gid_from(work, tgt_dense, remote_gids,
                                  state.dg.base, state.dg.bound)
@@ -488,7 +541,8 @@ def _ordered_sweep(state: PhaseState, cfg: LouvainConfig, move_fn,
     for vidx in color_order:
         inp = MoveInputs(state.dg.g.rowptr, state.halo.tails_dense,
                          state.dg.g.weights, work_dense, state.v_degree,
-                         c_size, c_degree, c_gid, state.constant)
+                         c_size, c_degree, c_gid, state.constant,
+                         local_gid_base=state.dg.base)
         tgt_dense, cw = move_fn(inp)
         mask = torch.zeros(nv, dtype=torch.bool, device=dev)
         mask[vidx] = True

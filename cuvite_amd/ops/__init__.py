@@ -109,8 +109,9 @@ def _hub_segsort_enabled() -> bool:
     R-MAT s26 (gpurun_out/ab/, profiles/): 189.7 ms/step vs 549.8 ms for
     the torch global-sort path (identical modularity trajectory), i.e. the
     hub stage drops 0.44 s -> 0.083 s. Narrow-bit segmented radix sort +
-    reduce_by_key + wave-per-hub argmax, fully device-side (no host sync
-    per iteration). CUVITE_HUB_SEGSORT=0 restores the torch-sort fallback."""
+    one sliced pass over the sorted pairs (run sums, gains, argmax), fully
+    device-side (no host sync per iteration). CUVITE_HUB_SEGSORT=0 restores
+    the torch-sort fallback."""
     return os.environ.get("CUVITE_HUB_SEGSORT", "1") not in ("0", "off")
 
 
@@ -141,19 +142,29 @@ def _hub_groups(inp, hubs, hdeg):
     return groups
 
 
-def _hub_moves_sorted(inp, hubs, hdeg):
+def _gid_args(inp) -> dict:
+    """Keyword arguments that tell the kernels which global community ids
+    they may compute instead of gathering (MoveInputs.local_gid_base)."""
+    base = getattr(inp, "local_gid_base", None)
+    if base is None:
+        return dict(gid_base=0, n_local=0)
+    return dict(gid_base=int(base), n_local=int(inp.nv))
+
+
+def _hub_moves_sorted(inp, hubs, hdeg, nxt=None):
     """Chunk wrapper: split the hub list into phase-static groups whose edge
     totals stay under the torch sort cap; each hub's candidates are
     independent. Returns (target_dense int32 [nhub], wcc [nhub]) aligned
-    with `hubs`."""
+    with `hubs`. `nxt`: optional (next_size, next_degree) pair; every group's
+    hub_moves call accounts its own hubs in it."""
     groups = _hub_groups(inp, hubs, hdeg)
     if len(groups) == 1:
-        return _hub_moves_sorted_one(inp, groups[0][0], groups[0][1])
+        return _hub_moves_sorted_one(inp, groups[0][0], groups[0][1], nxt)
     tgt = torch.empty(hubs.numel(), dtype=torch.int32, device=hubs.device)
     wcc = torch.empty(hubs.numel(), dtype=inp.weights.dtype,
                       device=hubs.device)
     for hubs_g, hdeg_g, m in groups:
-        t, w = _hub_moves_sorted_one(inp, hubs_g, hdeg_g)
+        t, w = _hub_moves_sorted_one(inp, hubs_g, hdeg_g, nxt)
         tgt[m] = t
         wcc[m] = w
     return tgt, wcc
@@ -218,7 +229,7 @@ def _hub_static(inp, hubs, hdeg):
         offs_d = torch.zeros(nhub + 1, dtype=torch.int64, device=dev)
         offs_d[1:] = torch.cumsum(
             torch.bincount(seg, minlength=nhub), dim=0)
-        extra = (tails_h.to(torch.int32), seg.to(torch.int32), offs_d,
+        extra = (tails_h.to(torch.int32), offs_d,
                  wts.to(inp.weights.dtype), hubs.to(torch.int32))
         seg = tails_h = wts = None
     else:
@@ -235,7 +246,7 @@ def _hub_static(inp, hubs, hdeg):
     return data
 
 
-def _hub_moves_sorted_one(inp, hubs, hdeg):
+def _hub_moves_sorted_one(inp, hubs, hdeg, nxt=None):
     """Hub vertices (deg > hub cut, default 6144) via radix sort +
     segmented reduction.
     Default path: the fully-device rocPRIM pipeline (hub_moves binding).
@@ -250,14 +261,21 @@ def _hub_moves_sorted_one(inp, hubs, hdeg):
     seg, tails_h, wts, selfloop, extra = _hub_static(inp, hubs, hdeg)
     C = inp.comm_degree.numel()
     if extra is not None:
-        # rocPRIM path, fully device-side: segmented narrow-bit radix sort
-        # + reduce_by_key + wave-per-hub argmax (no host sync per iteration)
-        tails32, seg32, offs, wts_w, hubs32 = extra
+        # rocPRIM path, fully device-side: segmented narrow-bit radix sort,
+        # then one sliced pass over the sorted pairs for run sums, gains
+        # and argmax (no host sync per iteration)
+        tails32, offs, wts_w, hubs32 = extra
         tgt_hub, cw_hub = _require().hub_moves(
-            tails32, wts_w, seg32, offs, hubs32, selfloop,
+            tails32, wts_w, offs, hubs32, selfloop,
             inp.curr_comm, inp.v_degree, inp.comm_size, inp.comm_degree,
-            inp.comm_gid, float(inp.constant))
+            inp.comm_gid, float(inp.constant), **_gid_args(inp),
+            next_size=None if nxt is None else nxt[0],
+            next_degree=None if nxt is None else nxt[1])
         return tgt_hub, cw_hub
+    if nxt is not None:
+        raise RuntimeError("fused aggregates need the rocPRIM hub path "
+                           "(CUVITE_HUB_SEGSORT=0 or a CPU tensor disables "
+                           "it)")
     comm = inp.curr_comm[tails_h].to(torch.int64)
     key = seg * C + comm
     del comm
@@ -310,9 +328,23 @@ def _hub_moves_sorted_one(inp, hubs, hdeg):
     return tgt_dense.to(torch.int32), wcc.to(inp.weights.dtype)
 
 
-def local_move(inp):
+def fused_aggregates_supported() -> bool:
+    """Whether local_move can account the new community aggregates itself
+    (next_size / next_degree): needs the rocPRIM hub path and the plain
+    (not per-class diagnostic) schedule."""
+    return _hub_segsort_enabled() and not os.environ.get("CUVITE_PROGRESS")
+
+
+def local_move(inp, next_size=None, next_degree=None):
     """HIP local-move iteration (see local_move.MoveInputs for semantics).
     Returns (target dense comm ids [nv], cluster_weight [nv]).
+
+    With `next_size` (int64) and `next_degree` (weight dtype), both of one
+    length >= nv, every vertex that has edges is also added to the size and
+    the degree of its target community in those buffers, by the kernel lane
+    that stores its target. The caller pre-loads them with what the edgeless
+    vertices contribute (those are never visited). The inputs' comm_size /
+    comm_degree must be other tensors: they are read while these are written.
 
     Degree classes 0-4 run in the LDS hash-table kernels; hub vertices
     (deg > _hub_cut()) go through the rocPRIM segsort pipeline
@@ -321,6 +353,14 @@ def local_move(inp):
     ext = _require()
     vlists, hubs64, hdeg = _buckets_for(inp.rowptr)
     dev = inp.rowptr.device
+    if (next_size is None) != (next_degree is None):
+        raise ValueError("next_size and next_degree go together")
+    nxt = None if next_size is None else (next_size, next_degree)
+    if nxt is not None and not fused_aggregates_supported():
+        raise RuntimeError("fused aggregates need the rocPRIM hub path and "
+                           "the plain schedule (CUVITE_HUB_SEGSORT=0 or "
+                           "CUVITE_PROGRESS is set)")
+    kw = dict(_gid_args(inp), next_size=next_size, next_degree=next_degree)
     if os.environ.get("CUVITE_PROGRESS"):
         import sys
         import time
@@ -335,7 +375,7 @@ def local_move(inp):
             outs.append(ext.local_move_bucketed(
                 inp.rowptr, inp.tails, inp.weights, inp.curr_comm,
                 inp.v_degree, inp.comm_size, inp.comm_degree, inp.comm_gid,
-                float(inp.constant), one))
+                float(inp.constant), one, **kw))
             torch.cuda.synchronize()
             print(f"[move] class {i} n={sizes[i]} "
                   f"{time.perf_counter() - t0:.3f}s", file=sys.stderr,
@@ -372,8 +412,8 @@ def local_move(inp):
             target, cw = ext.local_move_bucketed(
                 inp.rowptr, inp.tails, inp.weights, inp.curr_comm,
                 inp.v_degree, inp.comm_size, inp.comm_degree, inp.comm_gid,
-                float(inp.constant), vlists)
-        hub_tgt, hub_cw = _hub_moves_sorted(inp, hubs64, hdeg)
+                float(inp.constant), vlists, **kw)
+        hub_tgt, hub_cw = _hub_moves_sorted(inp, hubs64, hdeg, nxt)
         main.wait_stream(side)
         target.record_stream(main)
         cw.record_stream(main)
@@ -383,9 +423,9 @@ def local_move(inp):
     target, cw = ext.local_move_bucketed(
         inp.rowptr, inp.tails, inp.weights, inp.curr_comm, inp.v_degree,
         inp.comm_size, inp.comm_degree, inp.comm_gid, float(inp.constant),
-        vlists)
+        vlists, **kw)
     if run_hub_sort:
-        hub_tgt, hub_cw = _hub_moves_sorted(inp, hubs64, hdeg)
+        hub_tgt, hub_cw = _hub_moves_sorted(inp, hubs64, hdeg, nxt)
         target[hubs64] = hub_tgt
         cw[hubs64] = hub_cw
     return target, cw

@@ -22,6 +22,11 @@ struct MoveArgs {
   double constant;
   int32_t* target;
   W* cluster_weight;
+  int64_t gid_base;
+  int32_t n_local;
+  int64_t* next_size;
+  W* next_degree;
+  int64_t n_next;
 };
 
 template <typename W, int LANES, int CAP>
@@ -42,8 +47,6 @@ template <typename W>
 void launch_row_sum(const int64_t*, const W*, int64_t, W*, hipStream_t);
 void launch_gather_comm(const int32_t*, const int32_t*, int64_t, int32_t*,
                         hipStream_t);
-void launch_pack_key64(const int32_t*, const int32_t*, int64_t, int64_t,
-                       int64_t*, hipStream_t);
 template <typename W>
 void segsort_pairs(void*, size_t*, const int32_t*, int32_t*, const W*, W*,
                    int64_t, int, const int64_t*, int, hipStream_t);
@@ -54,12 +57,13 @@ template <typename W>
 void sort_pairs64(void*, size_t*, const int64_t*, int64_t*, const W*, W*,
                   int64_t, int, hipStream_t);
 template <typename W>
-void launch_hub_argmax(const int64_t*, const W*, const int32_t*, int64_t,
+void launch_hub_argmax(const int32_t*, const W*, const int64_t*,
                        const int32_t*, int, const double*, const int32_t*,
                        const W*, const int64_t*, const W*, const int64_t*,
-                       double, double*, int64_t*, int32_t*, int32_t*, W*,
-                       hipStream_t);
-int hub_argmax_splits();
+                       int64_t, int32_t, double, double*, double*, int64_t*,
+                       int32_t*, int32_t*, double*, int32_t*, W*, int64_t*,
+                       W*, int64_t, hipStream_t);
+int hub_slices();
 template <typename W>
 void launch_apply_deltas(const int64_t*, const int64_t*, const W*, int64_t,
                          int64_t, int64_t, int64_t*, W*, hipStream_t);
@@ -82,6 +86,31 @@ namespace {
 #define CHECK_DEV(t) TORCH_CHECK((t).is_cuda(), #t " must be on GPU")
 #define CHECK_CONT(t) TORCH_CHECK((t).is_contiguous(), #t " must be contiguous")
 
+// Optional second aggregate pair the move kernels account their targets in
+// (see account_target): both or neither, int64 sizes, degrees in the weight
+// dtype, equal lengths.
+void check_next(const c10::optional<at::Tensor>& next_size,
+                const c10::optional<at::Tensor>& next_degree,
+                const at::Tensor& weights) {
+  TORCH_CHECK(next_size.has_value() == next_degree.has_value(),
+              "next_size and next_degree go together");
+  if (!next_size.has_value()) return;
+  CHECK_DEV(*next_size); CHECK_CONT(*next_size);
+  CHECK_DEV(*next_degree); CHECK_CONT(*next_degree);
+  TORCH_CHECK(next_size->scalar_type() == at::kLong,
+              "next_size must be int64");
+  TORCH_CHECK(next_degree->scalar_type() == weights.scalar_type(),
+              "next_degree must have the weight dtype");
+  TORCH_CHECK(next_size->numel() == next_degree->numel(),
+              "next_size/next_degree length mismatch");
+}
+
+void check_local_gids(int64_t n_local, const at::Tensor& comm_gid) {
+  TORCH_CHECK(n_local >= 0 && n_local <= comm_gid.numel() &&
+              n_local <= (int64_t)INT32_MAX,
+              "n_local must lie in [0, number of communities]");
+}
+
 template <typename W>
 cuvite::MoveArgs<W> make_args(const at::Tensor& rowptr, const at::Tensor& tails,
                               const at::Tensor& weights,
@@ -90,14 +119,21 @@ cuvite::MoveArgs<W> make_args(const at::Tensor& rowptr, const at::Tensor& tails,
                               const at::Tensor& comm_size,
                               const at::Tensor& comm_degree,
                               const at::Tensor& comm_gid, double constant,
-                              at::Tensor& target, at::Tensor& cw) {
+                              at::Tensor& target, at::Tensor& cw,
+                              int64_t gid_base, int64_t n_local,
+                              const c10::optional<at::Tensor>& next_size,
+                              const c10::optional<at::Tensor>& next_degree) {
   return cuvite::MoveArgs<W>{
       rowptr.data_ptr<int64_t>(),   tails.data_ptr<int32_t>(),
       weights.data_ptr<W>(),        curr_comm.data_ptr<int32_t>(),
       v_degree.data_ptr<W>(),       comm_size.data_ptr<int64_t>(),
       comm_degree.data_ptr<W>(),    comm_gid.data_ptr<int64_t>(),
       constant,                     target.data_ptr<int32_t>(),
-      cw.data_ptr<W>()};
+      cw.data_ptr<W>(),             gid_base,
+      (int32_t)n_local,
+      next_size ? next_size->data_ptr<int64_t>() : nullptr,
+      next_degree ? next_degree->data_ptr<W>() : nullptr,
+      next_size ? next_size->numel() : 0};
 }
 
 // vlists: the 7 LDS degree-class vertex lists (hubs excluded)
@@ -107,7 +143,9 @@ std::vector<at::Tensor> local_move(
     at::Tensor rowptr, at::Tensor tails, at::Tensor weights,
     at::Tensor curr_comm, at::Tensor v_degree, at::Tensor comm_size,
     at::Tensor comm_degree, at::Tensor comm_gid, double constant,
-    std::vector<at::Tensor> vlists) {
+    std::vector<at::Tensor> vlists, int64_t gid_base, int64_t n_local,
+    c10::optional<at::Tensor> next_size,
+    c10::optional<at::Tensor> next_degree) {
   CHECK_DEV(rowptr); CHECK_CONT(rowptr);
   CHECK_DEV(tails); CHECK_CONT(tails);
   CHECK_DEV(weights); CHECK_CONT(weights);
@@ -116,6 +154,8 @@ std::vector<at::Tensor> local_move(
   TORCH_CHECK(curr_comm.scalar_type() == at::kInt, "curr_comm must be int32");
   TORCH_CHECK(vlists.size() == 7, "expected 7 degree-class vertex lists"
               " (hub vertices go through the hub_moves pipeline)");
+  check_local_gids(n_local, comm_gid);
+  check_next(next_size, next_degree, weights);
 
   const int64_t nv = rowptr.numel() - 1;
   auto target = curr_comm.narrow(0, 0, nv).clone();
@@ -126,7 +166,8 @@ std::vector<at::Tensor> local_move(
     using W = scalar_t;
     auto args = make_args<W>(rowptr, tails, weights, curr_comm, v_degree,
                              comm_size, comm_degree, comm_gid, constant,
-                             target, cw);
+                             target, cw, gid_base, n_local, next_size,
+                             next_degree);
     if (vlists[0].numel())
       cuvite::launch_sub<W, 16, 32>(vlists[0].data_ptr<int32_t>(),
                                     (int)vlists[0].numel(), args, stream);
@@ -216,22 +257,41 @@ std::vector<at::Tensor> csr_from_edges(int64_t nv, int64_t base,
   return {rowptr, tails, weights};
 }
 
-// Full hub move: gather -> segmented sort -> reduce_by_key -> wave-per-hub
-// argmax, all device-side (no host sync). Returns per-hub (target, wcc).
+// Full hub move, all device-side (no host sync): gather the neighbours'
+// communities -> segmented sort (community, weight) per hub -> one pass over
+// the sorted pairs in hub_slices() element slices per hub (own-community
+// weight, run sums, gains, partial argmax) -> per-hub stitch of the slice
+// records, guard and store. Scratch beyond the sort's is O(nhub * slices).
+// eoffs: int64 [nhub + 1] segment offsets into tails_flat / weights_flat.
+// Returns per-hub (target, wcc); with next_size / next_degree the hubs are
+// also accounted in that aggregate pair.
 std::vector<at::Tensor> hub_moves(
-    at::Tensor tails_flat, at::Tensor weights_flat, at::Tensor seg_flat,
-    at::Tensor eoffs, at::Tensor hubs_i32, at::Tensor hub_self,
-    at::Tensor curr_comm, at::Tensor v_degree, at::Tensor comm_size,
-    at::Tensor comm_degree, at::Tensor comm_gid, double constant) {
+    at::Tensor tails_flat, at::Tensor weights_flat, at::Tensor eoffs,
+    at::Tensor hubs_i32, at::Tensor hub_self, at::Tensor curr_comm,
+    at::Tensor v_degree, at::Tensor comm_size, at::Tensor comm_degree,
+    at::Tensor comm_gid, double constant, int64_t gid_base, int64_t n_local,
+    c10::optional<at::Tensor> next_size,
+    c10::optional<at::Tensor> next_degree) {
   CHECK_DEV(tails_flat); CHECK_CONT(tails_flat);
+  CHECK_DEV(weights_flat); CHECK_CONT(weights_flat);
+  CHECK_DEV(eoffs); CHECK_CONT(eoffs);
   CHECK_DEV(hubs_i32); CHECK_CONT(hubs_i32);
+  check_local_gids(n_local, comm_gid);
+  check_next(next_size, next_degree, weights_flat);
+  TORCH_CHECK(tails_flat.scalar_type() == at::kInt);
   TORCH_CHECK(hubs_i32.scalar_type() == at::kInt);
   TORCH_CHECK(hub_self.scalar_type() == at::kDouble);
+  TORCH_CHECK(eoffs.scalar_type() == at::kLong);
   const int64_t n = tails_flat.numel();
+  TORCH_CHECK(weights_flat.numel() == n, "tails/weights length mismatch");
   TORCH_CHECK(n < (int64_t)INT32_MAX,
               "hub candidate batch exceeds int32 count range; chunk the hubs");
   const int nhub = (int)hubs_i32.numel();
+  TORCH_CHECK(eoffs.numel() == (int64_t)nhub + 1 &&
+              hub_self.numel() == (int64_t)nhub,
+              "eoffs / hub_self do not match the hub list");
   const int64_t C = comm_degree.numel();
+  TORCH_CHECK(C < (int64_t)INT32_MAX, "community count exceeds int32");
   auto stream = at::hip::getCurrentHIPStream().stream();
   int end_bit = 1;
   while ((int64_t(1) << end_bit) < C) end_bit++;
@@ -259,43 +319,28 @@ std::vector<at::Tensor> hub_moves(
                              weights_flat.data_ptr<W>(), vals2.data_ptr<W>(),
                              n, nhub, eoffs.data_ptr<int64_t>(), end_bit,
                              stream);
-    auto key64 = at::empty({n}, eoffs.options());
-    cuvite::launch_pack_key64(keys2.data_ptr<int32_t>(),
-                              seg_flat.data_ptr<int32_t>(), n, C,
-                              key64.data_ptr<int64_t>(), stream);
-    auto uniq = at::empty({n}, eoffs.options());
-    auto sums = at::empty({n}, weights_flat.options());
-    auto cnt = at::zeros({1}, tails_flat.options());
-    size_t bytes2 = 0;
-    cuvite::reduce_by_key64<W>(nullptr, &bytes2, key64.data_ptr<int64_t>(),
-                               vals2.data_ptr<W>(), n,
-                               uniq.data_ptr<int64_t>(), sums.data_ptr<W>(),
-                               (unsigned int*)cnt.data_ptr<int32_t>(),
-                               stream);
-    auto temp2 = at::empty({(int64_t)bytes2},
-                           tails_flat.options().dtype(at::kByte));
-    cuvite::reduce_by_key64<W>(temp2.data_ptr(), &bytes2,
-                               key64.data_ptr<int64_t>(),
-                               vals2.data_ptr<W>(), n,
-                               uniq.data_ptr<int64_t>(), sums.data_ptr<W>(),
-                               (unsigned int*)cnt.data_ptr<int32_t>(),
-                               stream);
-    const int splits = cuvite::hub_argmax_splits();
-    auto p_gain = at::empty({(int64_t)nhub * splits},
-                            eoffs.options().dtype(at::kDouble));
-    auto p_gid = at::empty({(int64_t)nhub * splits},
-                           eoffs.options().dtype(at::kLong));
-    auto p_dense = at::empty({(int64_t)nhub * splits},
-                             tails_flat.options());
+    const int64_t nslice = (int64_t)nhub * cuvite::hub_slices();
+    auto f64 = eoffs.options().dtype(at::kDouble);
+    auto p_wcc = at::empty({nslice}, f64);
+    auto p_gain = at::empty({nslice}, f64);
+    auto p_gid = at::empty({nslice}, eoffs.options().dtype(at::kLong));
+    auto p_dense = at::empty({nslice}, tails_flat.options());
+    auto r_key = at::empty({2 * nslice}, tails_flat.options());
+    auto r_sum = at::empty({2 * nslice}, f64);
     cuvite::launch_hub_argmax<W>(
-        uniq.data_ptr<int64_t>(), sums.data_ptr<W>(),
-        cnt.data_ptr<int32_t>(), C, hubs_i32.data_ptr<int32_t>(), nhub,
+        keys2.data_ptr<int32_t>(), vals2.data_ptr<W>(),
+        eoffs.data_ptr<int64_t>(), hubs_i32.data_ptr<int32_t>(), nhub,
         hub_self.data_ptr<double>(), curr_comm.data_ptr<int32_t>(),
         v_degree.data_ptr<W>(), comm_size.data_ptr<int64_t>(),
-        comm_degree.data_ptr<W>(), comm_gid.data_ptr<int64_t>(), constant,
+        comm_degree.data_ptr<W>(), comm_gid.data_ptr<int64_t>(), gid_base,
+        (int32_t)n_local, constant, p_wcc.data_ptr<double>(),
         p_gain.data_ptr<double>(), p_gid.data_ptr<int64_t>(),
-        p_dense.data_ptr<int32_t>(),
-        target_hub.data_ptr<int32_t>(), cw_hub.data_ptr<W>(), stream);
+        p_dense.data_ptr<int32_t>(), r_key.data_ptr<int32_t>(),
+        r_sum.data_ptr<double>(), target_hub.data_ptr<int32_t>(),
+        cw_hub.data_ptr<W>(),
+        next_size ? next_size->data_ptr<int64_t>() : nullptr,
+        next_degree ? next_degree->data_ptr<W>() : nullptr,
+        next_size ? next_size->numel() : 0, stream);
   });
   C10_HIP_CHECK(hipGetLastError());
   return {target_hub, cw_hub};
@@ -482,7 +527,13 @@ at::Tensor intra_weight(at::Tensor rowptr, at::Tensor tails,
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("local_move_bucketed", &local_move,
-        "Louvain local-move iteration (HIP, degree-class routed)");
+        "Louvain local-move iteration (HIP, degree-class routed)",
+        py::arg("rowptr"), py::arg("tails"), py::arg("weights"),
+        py::arg("curr_comm"), py::arg("v_degree"), py::arg("comm_size"),
+        py::arg("comm_degree"), py::arg("comm_gid"), py::arg("constant"),
+        py::arg("vlists"), py::arg("gid_base") = 0, py::arg("n_local") = 0,
+        py::arg("next_size") = py::none(),
+        py::arg("next_degree") = py::none());
   m.def("modularity_parts", &modularity_parts,
         "fp64 (sum cw, sum degree^2) reduction (HIP)");
   m.def("scatter_add_", &scatter_add_,
@@ -503,6 +554,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "per-vertex weight into the own community, edge-balanced (HIP)");
   m.def("intra_weight_span", &cuvite::intra_weight_span,
         "edges per wave span of the intra_weight kernel");
+  m.def("hub_slices", &cuvite::hub_slices,
+        "element slices per hub segment in the hub argmax kernels");
   m.def("hub_moves", &hub_moves,
-        "full device-side hub move: segsort + reduce_by_key + argmax");
+        "full device-side hub move: segsort + sliced run-sum argmax",
+        py::arg("tails_flat"), py::arg("weights_flat"), py::arg("eoffs"), py::arg("hubs_i32"), py::arg("hub_self"),
+        py::arg("curr_comm"), py::arg("v_degree"), py::arg("comm_size"),
+        py::arg("comm_degree"), py::arg("comm_gid"), py::arg("constant"),
+        py::arg("gid_base") = 0, py::arg("n_local") = 0,
+        py::arg("next_size") = py::none(),
+        py::arg("next_degree") = py::none());
 }

@@ -24,9 +24,12 @@
 //                                cut = CUVITE_HUB_CUT, default 6144 after
 //                                the s26 A/B in profiles/)
 //   hub    : deg > cut (6144)    hub_moves binding (rocPRIM narrow-bit
-//                                segmented radix sort + reduce_by_key +
-//                                split-block argmax) — 2.9x faster than
-//                                the torch global-sort fallback at s26
+//                                segmented radix sort, then one pass over
+//                                the sorted pairs in fixed element slices:
+//                                run sums, gains and argmax, see "Hub
+//                                argmax straight from the sorted pairs"
+//                                below) — the sort pipeline is 2.9x faster
+//                                than the torch global-sort fallback at s26
 //                                (A/B in profiles/; CUVITE_HUB_SEGSORT=0
 //                                restores the fallback). A global-memory
 //                                hash-table hub pipeline existed in round
@@ -39,6 +42,10 @@
 //
 // All gain arithmetic is fp64 regardless of the weight dtype so trajectories
 // match the fp64 CPU oracle (tie-break on equal gains -> smaller GLOBAL id).
+// Global ids of locally owned communities are computed, not gathered
+// (gid_of); with a second aggregate pair the lanes that store a target also
+// account the new community sizes and degrees (account_target), which
+// replaces the recount pass after a single-rank sweep.
 
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
@@ -82,6 +89,31 @@ DEV_INLINE void best_combine(Best& a, double g, int64_t gid, int32_t dense) {
     a.gid = gid;
     a.dense = dense;
   }
+}
+
+// Global id of dense community y. Locally owned communities occupy the dense
+// ids [0, n_local) and their global id is gid_base + y by construction, so
+// the 8-byte random read of comm_gid[y] is needed for remote ones only.
+// n_local == 0 reads the table for every id.
+DEV_INLINE int64_t gid_of(const int64_t* __restrict__ comm_gid,
+                          int64_t gid_base, int32_t n_local, int32_t y) {
+  return y < n_local ? gid_base + (int64_t)y : comm_gid[y];
+}
+
+// Fused aggregate accounting: the lane that stores target[v] = tgt also adds
+// v to the size and the degree of its new community in a second aggregate
+// pair, so no recount pass over the labels is needed after the sweep. The
+// atomics are fire-and-forget (no returned value). next_size == nullptr
+// turns it off; the range check is the memory-safety guard recount_kernel
+// has (an out-of-range label must not corrupt memory).
+template <typename W>
+DEV_INLINE void account_target(int64_t* __restrict__ next_size,
+                               W* __restrict__ next_degree, int64_t n_next,
+                               int32_t tgt, W vdeg) {
+  if (next_size == nullptr) return;
+  if (tgt < 0 || (int64_t)tgt >= n_next) return;
+  atomicAdd((unsigned long long*)&next_size[tgt], 1ull);
+  unsafeAtomicAdd(&next_degree[tgt], vdeg);
 }
 
 template <int WIDTH> DEV_INLINE void best_reduce(Best& b) {
@@ -172,14 +204,15 @@ DEV_INLINE void scan_slots(const int32_t* keys, const W* vals, int cap,
                            int lane, int lanes, int32_t cc, double eix,
                            double ax, double vdeg, double constant,
                            const W* __restrict__ comm_degree,
-                           const int64_t* __restrict__ comm_gid, Best& best) {
+                           const int64_t* __restrict__ comm_gid,
+                           int64_t gid_base, int32_t n_local, Best& best) {
   for (int s = lane; s < cap; s += lanes) {
     int32_t y = keys[s];
     if (y == EMPTY_KEY || y == cc) continue;
     double eiy = (double)vals[s];
     double ay = (double)comm_degree[y];
     double g = 2.0 * (eiy - eix) - 2.0 * vdeg * (ay - ax) * constant;
-    best_combine(best, g, comm_gid[y], y);
+    best_combine(best, g, gid_of(comm_gid, gid_base, n_local, y), y);
   }
 }
 
@@ -207,7 +240,9 @@ __global__ __launch_bounds__(BLOCK) void lv_move_sub(
     const W* __restrict__ v_degree, const int64_t* __restrict__ comm_size,
     const W* __restrict__ comm_degree, const int64_t* __restrict__ comm_gid,
     double constant, int32_t* __restrict__ target,
-    W* __restrict__ cluster_weight) {
+    W* __restrict__ cluster_weight, int64_t gid_base, int32_t n_local,
+    int64_t* __restrict__ next_size, W* __restrict__ next_degree,
+    int64_t n_next) {
   constexpr int GROUPS = BLOCK / LANES;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   W* vals = (W*)smem;
@@ -245,19 +280,22 @@ __global__ __launch_bounds__(BLOCK) void lv_move_sub(
   if (v >= 0 && e0 != e1) {
     W wcc = table_probe(gkeys, gvals, cap, cc);  // counter[cc]
     double eix = (double)wcc - __shfl(selfloop, 0, LANES);
-    double vdeg = (double)v_degree[v];
+    const W vdeg_w = v_degree[v];
+    double vdeg = (double)vdeg_w;
     double ax = (double)comm_degree[cc] - vdeg;
-    best.gid = comm_gid[cc];
+    const int64_t gid_cc = gid_of(comm_gid, gid_base, n_local, cc);
+    best.gid = gid_cc;
     scan_slots(gkeys, gvals, cap, lane, LANES, cc, eix, ax, vdeg, constant,
-               comm_degree, comm_gid, best);
+               comm_degree, comm_gid, gid_base, n_local, best);
     best_reduce<LANES>(best);
     if (lane == 0) {
       int32_t tgt = best.dense;
       // singleton-swap guard (louvain.cpp:2238-2239)
-      if (comm_size[tgt] == 1 && comm_size[cc] == 1 && best.gid > comm_gid[cc])
+      if (comm_size[tgt] == 1 && comm_size[cc] == 1 && best.gid > gid_cc)
         tgt = cc;
       target[v] = tgt;
       cluster_weight[v] = wcc;
+      account_target(next_size, next_degree, n_next, tgt, vdeg_w);
     }
   }
 }
@@ -274,7 +312,9 @@ __global__ __launch_bounds__(BLOCK) void lv_move_block(
     const W* __restrict__ v_degree, const int64_t* __restrict__ comm_size,
     const W* __restrict__ comm_degree, const int64_t* __restrict__ comm_gid,
     double constant, int32_t* __restrict__ target,
-    W* __restrict__ cluster_weight) {
+    W* __restrict__ cluster_weight, int64_t gid_base, int32_t n_local,
+    int64_t* __restrict__ next_size, W* __restrict__ next_degree,
+    int64_t n_next) {
   constexpr int WAVES = BLOCK / 64;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   W* vals = (W*)smem;
@@ -309,11 +349,13 @@ __global__ __launch_bounds__(BLOCK) void lv_move_block(
 
   W wcc = table_probe(keys, vals, cap, cc);
   double eix = (double)wcc - self_total;
-  double vdeg = (double)v_degree[v];
+  const W vdeg_w = v_degree[v];
+  double vdeg = (double)vdeg_w;
   double ax = (double)comm_degree[cc] - vdeg;
-  Best best{0.0, comm_gid[cc], cc};
+  const int64_t gid_cc = gid_of(comm_gid, gid_base, n_local, cc);
+  Best best{0.0, gid_cc, cc};
   scan_slots(keys, vals, cap, tid, BLOCK, cc, eix, ax, vdeg, constant,
-             comm_degree, comm_gid, best);
+             comm_degree, comm_gid, gid_base, n_local, best);
   best_reduce<64>(best);
   if (lane == 0) {
     red_gain[wave] = best.gain;
@@ -326,10 +368,11 @@ __global__ __launch_bounds__(BLOCK) void lv_move_block(
     for (int i = 1; i < WAVES; i++)
       best_combine(best, red_gain[i], red_gid[i], red_dense[i]);
     int32_t tgt = best.dense;
-    if (comm_size[tgt] == 1 && comm_size[cc] == 1 && best.gid > comm_gid[cc])
+    if (comm_size[tgt] == 1 && comm_size[cc] == 1 && best.gid > gid_cc)
       tgt = cc;
     target[v] = tgt;
     cluster_weight[v] = wcc;
+    account_target(next_size, next_degree, n_next, tgt, vdeg_w);
   }
 }
 
@@ -678,11 +721,11 @@ __global__ __launch_bounds__(BLOCK) void intra_weight_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// Hub candidate generation via rocPRIM (CUVITE_HUB_SEGSORT experiment):
-// per-hub segmented radix sort of the community keys (only ceil(log2 C) bits)
-// + reduce_by_key for the (hub, community) weight sums. The torch path sorts
-// full 64-bit packed keys; narrow-bit segmented sort does ~half the radix
-// passes.
+// Hub candidate generation via rocPRIM: gather the neighbours' community
+// ids, then a per-hub segmented radix sort of those keys (only
+// ceil(log2 C) bits) with the edge weights as payload. The torch fallback
+// sorts full 64-bit packed keys; the narrow-bit segmented sort does about
+// half the radix passes.
 // ---------------------------------------------------------------------------
 
 __global__ void gather_comm_kernel(const int32_t* __restrict__ tails_flat,
@@ -694,127 +737,260 @@ __global__ void gather_comm_kernel(const int32_t* __restrict__ tails_flat,
     keys[i] = curr_comm[tails_flat[i]];
 }
 
-__global__ void pack_key64_kernel(const int32_t* __restrict__ keys,
-                                  const int32_t* __restrict__ seg_flat,
-                                  int64_t n, int64_t C,
-                                  int64_t* __restrict__ key64) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += stride)
-    key64[i] = (int64_t)seg_flat[i] * C + keys[i];
+// ---------------------------------------------------------------------------
+// Hub argmax straight from the sorted (community, weight) pairs: after the
+// segmented sort every hub's segment [eoffs[h], eoffs[h+1]) of keys2/vals2
+// holds its neighbour communities in ascending order, equal ones adjacent
+// (a "run"). Three kernels read that once (12 B per hub edge) and write
+// only O(nhub * HUB_SLICES) scratch:
+//
+//   hub_own_weight_kernel  the weight into the hub's own community cc is a
+//       constant inside every gain, so it has to exist before any gain is
+//       evaluated: a wave-cooperative 64-ary search finds the run of cc and
+//       the run is summed in HUB_SLICES equal shares (it can hold 10^5-10^6
+//       edges), one partial per wave.
+//   hub_slice_kernel       the segment is cut into HUB_SLICES equal element
+//       slices, one wave each, so the work per wave is bounded by elements
+//       however long a run is (the mega-hub imbalance the split argmax was
+//       introduced for, profiles/round2_kernel_stats). A wave walks its
+//       slice in 64-element chunks with a segmented shuffle scan and a
+//       (key, sum) carry between chunks (the intra_weight_kernel pattern),
+//       evaluates the gain of every run that lies wholly inside the slice at
+//       the run's last lane, and hands the slice's first and last run, which
+//       may continue in a neighbour slice, on as (key, sum) records.
+//   hub_final_kernel       one wave per hub, one record per lane: records
+//       with equal keys are pieces of one run (the segment is sorted) and
+//       are summed in slice order, their gains evaluated, the partial bests
+//       folded, the singleton guard applied, target and cw written and, on
+//       the fused path, the new community aggregates accounted.
+//
+// Every sum is fp64 in an order fixed by the slice layout (no float atomics
+// on weights), rounded to the weight type once per run like the LDS tables'
+// entries; gains use the class kernels' expression and operand order.
+// ---------------------------------------------------------------------------
+
+constexpr int HUB_SLICES = 32;   // 2 records per slice = one per final lane
+constexpr int HUB_PIPE = 4;      // chunks of loads in flight per wave
+static_assert(2 * HUB_SLICES == 64, "hub_final_kernel: one record per lane");
+
+// First index i in [lo, hi) with a[i] >= key, hi if none; a ascending on
+// [lo, hi). All 64 lanes take part and get the same answer: each round
+// probes 64 evenly spaced elements, so a 10^6-element segment takes 4
+// dependent loads instead of 20.
+DEV_INLINE int64_t wave_lower_bound(const int32_t* __restrict__ a, int64_t lo,
+                                    int64_t hi, int32_t key, int lane) {
+  while (hi - lo > 64) {
+    const int64_t step = (hi - lo + 63) / 64;
+    const int64_t p = lo + (int64_t)lane * step;
+    const bool ge = (p < hi) ? (a[p] >= key) : true;
+    const unsigned long long m = __ballot(ge);
+    if (m == 0ull) {            // all 64 probes in range and below key
+      lo = lo + 63 * step + 1;
+      continue;
+    }
+    const int f = __ffsll(m) - 1;
+    if (f == 0) return lo;      // a[lo] >= key
+    const int64_t pf = lo + (int64_t)f * step;
+    lo = lo + (int64_t)(f - 1) * step + 1;
+    hi = pf < hi ? pf : hi;
+  }
+  const int64_t p = lo + lane;
+  const bool ge = (p < hi) ? (a[p] >= key) : true;
+  const unsigned long long m = __ballot(ge);
+  return m ? lo + (__ffsll(m) - 1) : hi;
 }
 
-// dQ argmax over the per-hub (sorted, deduped) candidate ranges produced by
-// reduce_by_key. Two facts make this cheap: (a) keys are UNIQUE, so the
-// weight to the own community wcc is a single binary search, not a range
-// scan; (b) the argmax over a hub's range is split across ARGMAX_SPLITS
-// blocks so an R-MAT mega-hub (10^6 candidates) cannot serialize on one
-// wave — rocprof at s26 showed the wave-per-hub version at 20-45 ms/sweep
-// from exactly that imbalance (profiles/round2_kernel_stats).
-
-constexpr int ARGMAX_SPLITS = 8;
-
-DEV_INLINE int64_t lower_bound64(const int64_t* __restrict__ a, int64_t n,
-                                 int64_t key) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t m = (lo + hi) >> 1;
-    if (a[m] < key) lo = m + 1; else hi = m;
-  }
-  return lo;
+// Sum of the HUB_SLICES own-weight partials of hub `hidx`, in one fixed
+// order (same bits in every wave that asks).
+DEV_INLINE double hub_own_weight(const double* __restrict__ p_wcc, int hidx,
+                                 int lane) {
+  const double v =
+      lane < HUB_SLICES ? p_wcc[(int64_t)hidx * HUB_SLICES + lane] : 0.0;
+  return __shfl(sum_reduce<64>(v), 0, 64);
 }
 
 template <typename W, int BLOCK>
-__global__ __launch_bounds__(BLOCK) void hub_argmax_part_kernel(
-    const int64_t* __restrict__ uniq, const W* __restrict__ sums,
-    const int32_t* __restrict__ cnt_ptr, int64_t C,
-    const int32_t* __restrict__ hubs, int nhub,
-    const double* __restrict__ hub_self,
-    const int32_t* __restrict__ curr_comm, const W* __restrict__ v_degree,
-    const W* __restrict__ comm_degree, const int64_t* __restrict__ comm_gid,
-    double constant, double* __restrict__ p_gain,
-    int64_t* __restrict__ p_gid, int32_t* __restrict__ p_dense) {
+__global__ __launch_bounds__(BLOCK) void hub_own_weight_kernel(
+    const int32_t* __restrict__ keys, const W* __restrict__ vals,
+    const int64_t* __restrict__ eoffs, const int32_t* __restrict__ hubs,
+    int nhub, const int32_t* __restrict__ curr_comm,
+    double* __restrict__ p_wcc) {
   constexpr int WAVES = BLOCK / 64;
-  __shared__ double red_gain[WAVES];
-  __shared__ int64_t red_gid[WAVES];
-  __shared__ int32_t red_dense[WAVES];
-  const int hidx = blockIdx.x / ARGMAX_SPLITS;
-  const int part = blockIdx.x % ARGMAX_SPLITS;
-  const int64_t n = (int64_t)cnt_ptr[0];
+  const int lane = threadIdx.x % 64;
+  const int64_t w = (int64_t)blockIdx.x * WAVES + threadIdx.x / 64;
+  const int hidx = (int)(w / HUB_SLICES);
+  const int part = (int)(w % HUB_SLICES);
+  if (hidx >= nhub) return;
+  const int32_t cc = curr_comm[hubs[hidx]];
+  const int64_t b = eoffs[hidx], e = eoffs[hidx + 1];
+  const int64_t r0 = wave_lower_bound(keys, b, e, cc, lane);
+  // keys are dense community ids < 2^31 - 1, so cc + 1 does not overflow
+  const int64_t r1 = wave_lower_bound(keys, r0, e, cc + 1, lane);
+  const int64_t len = r1 - r0;
+  const int64_t s0 = r0 + part * len / HUB_SLICES;
+  const int64_t s1 = r0 + (part + 1) * len / HUB_SLICES;
+  double acc = 0.0;
+  for (int64_t i = s0 + lane; i < s1; i += 64) acc += (double)vals[i];
+  acc = sum_reduce<64>(acc);
+  if (lane == 0) p_wcc[w] = acc;
+}
+
+template <typename W, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void hub_slice_kernel(
+    const int32_t* __restrict__ keys, const W* __restrict__ vals,
+    const int64_t* __restrict__ eoffs, const int32_t* __restrict__ hubs,
+    int nhub, const double* __restrict__ hub_self,
+    const double* __restrict__ p_wcc, const int32_t* __restrict__ curr_comm,
+    const W* __restrict__ v_degree, const W* __restrict__ comm_degree,
+    const int64_t* __restrict__ comm_gid, int64_t gid_base, int32_t n_local,
+    double constant, double* __restrict__ p_gain, int64_t* __restrict__ p_gid,
+    int32_t* __restrict__ p_dense, int32_t* __restrict__ r_key,
+    double* __restrict__ r_sum) {
+  constexpr int WAVES = BLOCK / 64;
+  const int lane = threadIdx.x % 64;
+  const int64_t w = (int64_t)blockIdx.x * WAVES + threadIdx.x / 64;
+  const int hidx = (int)(w / HUB_SLICES);
+  const int part = (int)(w % HUB_SLICES);
+  if (hidx >= nhub) return;
   const int32_t v = hubs[hidx];
   const int32_t cc = curr_comm[v];
-  const int64_t keylo = (int64_t)hidx * C;
-  const int64_t r0 = lower_bound64(uniq, n, keylo);
-  const int64_t r1 = lower_bound64(uniq, n, keylo + C);
-  // unique keys: the own-community weight is one lookup
-  const int64_t pcc = lower_bound64(uniq, n, keylo + cc);
-  const double wcc =
-      (pcc < n && uniq[pcc] == keylo + cc) ? (double)sums[pcc] : 0.0;
-  const double eix = wcc - hub_self[hidx];
+  const int64_t b = eoffs[hidx], e = eoffs[hidx + 1];
+  const int64_t len = e - b;
+  const int64_t s0 = b + part * len / HUB_SLICES;
+  const int64_t s1 = b + (part + 1) * len / HUB_SLICES;
+  Best best{0.0, gid_of(comm_gid, gid_base, n_local, cc), cc};
+  if (s0 == s1) {  // wave-uniform: a segment shorter than HUB_SLICES
+    if (lane == 0) {
+      r_key[2 * w] = EMPTY_KEY;
+      r_key[2 * w + 1] = EMPTY_KEY;
+      p_gain[w] = best.gain;
+      p_gid[w] = best.gid;
+      p_dense[w] = best.dense;
+    }
+    return;
+  }
+  const W wcc = (W)hub_own_weight(p_wcc, hidx, lane);
+  const double eix = (double)wcc - hub_self[hidx];
   const double vdeg = (double)v_degree[v];
   const double ax = (double)comm_degree[cc] - vdeg;
-  const int64_t len = r1 - r0;
-  const int64_t s0 = r0 + part * len / ARGMAX_SPLITS;
-  const int64_t s1 = r0 + (part + 1) * len / ARGMAX_SPLITS;
-  Best best{0.0, comm_gid[cc], cc};
-  for (int64_t i = s0 + threadIdx.x; i < s1; i += BLOCK) {
-    const int32_t y = (int32_t)(uniq[i] - keylo);
-    if (y == cc) continue;
-    const double eiy = (double)sums[i];
-    const double ay = (double)comm_degree[y];
-    const double g = 2.0 * (eiy - eix) - 2.0 * vdeg * (ay - ax) * constant;
-    best_combine(best, g, comm_gid[y], y);
+  // the runs of these two keys may go on in a neighbour slice
+  const int32_t first_key = keys[s0], last_key = keys[s1 - 1];
+
+  double carry_sum = 0.0;
+  int32_t carry_key = EMPTY_KEY;  // key whose run the last chunk left open
+  for (int64_t c = s0; c < s1; c += (int64_t)HUB_PIPE * 64) {
+    int32_t k[HUB_PIPE], kn[HUB_PIPE];
+    W x[HUB_PIPE];
+#pragma unroll
+    for (int j = 0; j < HUB_PIPE; j++) {
+      const int64_t i = c + j * 64 + lane;
+      k[j] = i < s1 ? keys[i] : -2;           // past the slice: inert run
+      x[j] = i < s1 ? vals[i] : (W)0;
+      kn[j] = i + 1 < s1 ? keys[i + 1] : -3;  // the slice's last lane: tail
+    }
+#pragma unroll
+    for (int j = 0; j < HUB_PIPE; j++) {
+      if (c + j * 64 >= s1) break;  // wave-uniform
+      const int32_t kk = k[j];
+      double val = (double)x[j];
+      if (lane == 0 && kk == carry_key) val += carry_sum;
+      // segmented inclusive scan: equal keys are contiguous lanes
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const double pv = __shfl_up(val, off, 64);
+        const int32_t pk = __shfl_up(kk, off, 64);
+        if (lane >= off && pk == kk) val += pv;
+      }
+      const bool tail = kk >= 0 && kn[j] != kk;
+      if (tail) {
+        if (kk == first_key) {
+          r_key[2 * w] = kk;
+          r_sum[2 * w] = val;
+        } else if (kk == last_key) {
+          r_key[2 * w + 1] = kk;
+          r_sum[2 * w + 1] = val;
+        } else if (kk != cc) {
+          const double eiy = (double)(W)val;
+          const double ay = (double)comm_degree[kk];
+          const double g =
+              2.0 * (eiy - eix) - 2.0 * vdeg * (ay - ax) * constant;
+          best_combine(best, g, gid_of(comm_gid, gid_base, n_local, kk), kk);
+        }
+      }
+      // only a full chunk can end inside a run
+      carry_sum = __shfl(val, 63, 64);
+      carry_key = __shfl(tail ? EMPTY_KEY : kk, 63, 64);
+    }
   }
   best_reduce<64>(best);
-  const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
   if (lane == 0) {
-    red_gain[wave] = best.gain;
-    red_gid[wave] = best.gid;
-    red_dense[wave] = best.dense;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int i = 1; i < WAVES; i++)
-      best_combine(best, red_gain[i], red_gid[i], red_dense[i]);
-    p_gain[blockIdx.x] = best.gain;
-    p_gid[blockIdx.x] = best.gid;
-    p_dense[blockIdx.x] = best.dense;
+    if (first_key == last_key) r_key[2 * w + 1] = EMPTY_KEY;
+    p_gain[w] = best.gain;
+    p_gid[w] = best.gid;
+    p_dense[w] = best.dense;
   }
 }
 
 template <typename W, int BLOCK>
-__global__ __launch_bounds__(BLOCK) void hub_argmax_final_kernel(
-    const int64_t* __restrict__ uniq, const W* __restrict__ sums,
-    const int32_t* __restrict__ cnt_ptr, int64_t C,
+__global__ __launch_bounds__(BLOCK) void hub_final_kernel(
     const int32_t* __restrict__ hubs, int nhub,
-    const int32_t* __restrict__ curr_comm,
-    const int64_t* __restrict__ comm_size, const int64_t* __restrict__ comm_gid,
-    const double* __restrict__ p_gain, const int64_t* __restrict__ p_gid,
-    const int32_t* __restrict__ p_dense, int32_t* __restrict__ target_hub,
-    W* __restrict__ cw_hub) {
+    const double* __restrict__ hub_self, const double* __restrict__ p_wcc,
+    const int32_t* __restrict__ curr_comm, const W* __restrict__ v_degree,
+    const int64_t* __restrict__ comm_size, const W* __restrict__ comm_degree,
+    const int64_t* __restrict__ comm_gid, int64_t gid_base, int32_t n_local,
+    double constant, const double* __restrict__ p_gain,
+    const int64_t* __restrict__ p_gid, const int32_t* __restrict__ p_dense,
+    const int32_t* __restrict__ r_key, const double* __restrict__ r_sum,
+    int32_t* __restrict__ target_hub, W* __restrict__ cw_hub,
+    int64_t* __restrict__ next_size, W* __restrict__ next_degree,
+    int64_t n_next) {
   constexpr int WAVES = BLOCK / 64;
   const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
   const int hidx = blockIdx.x * WAVES + wave;
   if (hidx >= nhub) return;
-  const int64_t n = (int64_t)cnt_ptr[0];
   const int32_t v = hubs[hidx];
   const int32_t cc = curr_comm[v];
-  Best best{0.0, comm_gid[cc], cc};
-  if (lane < ARGMAX_SPLITS) {
-    const int p = hidx * ARGMAX_SPLITS + lane;
+  const W wcc = (W)hub_own_weight(p_wcc, hidx, lane);
+  const double eix = (double)wcc - hub_self[hidx];
+  const W vdeg_w = v_degree[v];
+  const double vdeg = (double)vdeg_w;
+  const double ax = (double)comm_degree[cc] - vdeg;
+  const int64_t gid_cc = gid_of(comm_gid, gid_base, n_local, cc);
+  Best best{0.0, gid_cc, cc};
+  if (lane < HUB_SLICES) {
+    const int64_t p = (int64_t)hidx * HUB_SLICES + lane;
     best = Best{p_gain[p], p_gid[p], p_dense[p]};
+  }
+  // lane = record (2 * slice + {first, last}), i.e. records in slice order
+  const int64_t r = (int64_t)hidx * 2 * HUB_SLICES + lane;
+  const int32_t key = r_key[r];
+  const double sum = key >= 0 ? r_sum[r] : 0.0;
+  double total = 0.0;
+  bool leader = key >= 0;  // lowest lane of its key evaluates the run
+#pragma unroll 4
+  for (int j = 0; j < 64; j++) {
+    const int32_t kj = __shfl(key, j, 64);
+    const double sj = __shfl(sum, j, 64);
+    if (kj == key) {
+      total += sj;
+      if (j < lane) leader = false;
+    }
+  }
+  if (leader && key != cc) {
+    const double eiy = (double)(W)total;
+    const double ay = (double)comm_degree[key];
+    const double g = 2.0 * (eiy - eix) - 2.0 * vdeg * (ay - ax) * constant;
+    best_combine(best, g, gid_of(comm_gid, gid_base, n_local, key), key);
   }
   best_reduce<64>(best);
   if (lane == 0) {
     int32_t tgt = best.dense;
-    if (comm_size[tgt] == 1 && comm_size[cc] == 1 && best.gid > comm_gid[cc])
+    // singleton-swap guard (louvain.cpp:2238-2239)
+    if (comm_size[tgt] == 1 && comm_size[cc] == 1 && best.gid > gid_cc)
       tgt = cc;
     target_hub[hidx] = tgt;
-    const int64_t keycc = (int64_t)hidx * C + cc;
-    const int64_t pcc = lower_bound64(uniq, n, keycc);
-    cw_hub[hidx] =
-        (pcc < n && uniq[pcc] == keycc) ? sums[pcc] : (W)0;
+    cw_hub[hidx] = wcc;
+    account_target(next_size, next_degree, n_next, tgt, vdeg_w);
   }
 }
 
@@ -840,6 +1016,11 @@ struct MoveArgs {
   double constant;
   int32_t* target;
   W* cluster_weight;
+  int64_t gid_base;     // gid(y) = gid_base + y for y < n_local (gid_of)
+  int32_t n_local;      // 0: every gid is read from comm_gid
+  int64_t* next_size;   // fused aggregates (account_target); null = off
+  W* next_degree;
+  int64_t n_next;       // length of next_size / next_degree
 };
 
 template <typename W, int LANES, int CAP>
@@ -857,7 +1038,8 @@ void launch_sub(const int32_t* vlist, int nlist, const MoveArgs<W>& a,
   hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), shmem, stream, vlist,
                      nlist, a.rowptr, a.tails, a.weights, a.curr_comm,
                      a.v_degree, a.comm_size, a.comm_degree, a.comm_gid,
-                     a.constant, a.target, a.cluster_weight);
+                     a.constant, a.target, a.cluster_weight, a.gid_base,
+                     a.n_local, a.next_size, a.next_degree, a.n_next);
 }
 
 template <typename W, int CAP>
@@ -873,7 +1055,8 @@ void launch_block(const int32_t* vlist, int nlist, const MoveArgs<W>& a,
   hipLaunchKernelGGL(kern, dim3(nlist), dim3(BLOCK), shmem, stream, vlist,
                      nlist, a.rowptr, a.tails, a.weights, a.curr_comm,
                      a.v_degree, a.comm_size, a.comm_degree, a.comm_gid,
-                     a.constant, a.target, a.cluster_weight);
+                     a.constant, a.target, a.cluster_weight, a.gid_base,
+                     a.n_local, a.next_size, a.next_degree, a.n_next);
 }
 
 // explicit instantiations used by bindings.cpp
@@ -1015,54 +1198,47 @@ void launch_gather_comm(const int32_t* tails_flat, const int32_t* curr_comm,
                      stream, tails_flat, curr_comm, n, keys);
 }
 
-void launch_pack_key64(const int32_t* keys, const int32_t* seg_flat,
-                       int64_t n, int64_t C, int64_t* key64,
-                       hipStream_t stream) {
-  if (n == 0) return;
-  hipLaunchKernelGGL(pack_key64_kernel, dim3(grid_for(n, 256)), dim3(256), 0,
-                     stream, keys, seg_flat, n, C, key64);
-}
-
 template <typename W>
-void launch_hub_argmax(const int64_t* uniq, const W* sums,
-                       const int32_t* cnt, int64_t C, const int32_t* hubs,
-                       int nhub, const double* hub_self,
-                       const int32_t* curr_comm, const W* v_degree,
-                       const int64_t* comm_size, const W* comm_degree,
-                       const int64_t* comm_gid, double constant,
-                       double* p_gain, int64_t* p_gid, int32_t* p_dense,
-                       int32_t* target_hub, W* cw_hub, hipStream_t stream) {
+void launch_hub_argmax(const int32_t* keys, const W* vals,
+                       const int64_t* eoffs, const int32_t* hubs, int nhub,
+                       const double* hub_self, const int32_t* curr_comm,
+                       const W* v_degree, const int64_t* comm_size,
+                       const W* comm_degree, const int64_t* comm_gid,
+                       int64_t gid_base, int32_t n_local, double constant,
+                       double* p_wcc, double* p_gain, int64_t* p_gid,
+                       int32_t* p_dense, int32_t* r_key, double* r_sum,
+                       int32_t* target_hub, W* cw_hub, int64_t* next_size,
+                       W* next_degree, int64_t n_next, hipStream_t stream) {
   if (nhub == 0) return;
   constexpr int BLOCK = 256;
   constexpr int WAVES = BLOCK / 64;
-  hipLaunchKernelGGL((hub_argmax_part_kernel<W, BLOCK>),
-                     dim3(nhub * ARGMAX_SPLITS), dim3(BLOCK), 0, stream,
-                     uniq, sums, cnt, C, hubs, nhub, hub_self, curr_comm,
-                     v_degree, comm_degree, comm_gid, constant, p_gain,
-                     p_gid, p_dense);
-  hipLaunchKernelGGL((hub_argmax_final_kernel<W, BLOCK>),
+  static_assert(HUB_SLICES % WAVES == 0, "whole blocks per hub");
+  const dim3 slice_grid((uint32_t)nhub * (HUB_SLICES / WAVES));
+  hipLaunchKernelGGL((hub_own_weight_kernel<W, BLOCK>), slice_grid,
+                     dim3(BLOCK), 0, stream, keys, vals, eoffs, hubs, nhub,
+                     curr_comm, p_wcc);
+  hipLaunchKernelGGL((hub_slice_kernel<W, BLOCK>), slice_grid, dim3(BLOCK), 0,
+                     stream, keys, vals, eoffs, hubs, nhub, hub_self, p_wcc,
+                     curr_comm, v_degree, comm_degree, comm_gid, gid_base,
+                     n_local, constant, p_gain, p_gid, p_dense, r_key, r_sum);
+  hipLaunchKernelGGL((hub_final_kernel<W, BLOCK>),
                      dim3((nhub + WAVES - 1) / WAVES), dim3(BLOCK), 0, stream,
-                     uniq, sums, cnt, C, hubs, nhub, curr_comm, comm_size,
-                     comm_gid, p_gain, p_gid, p_dense, target_hub, cw_hub);
+                     hubs, nhub, hub_self, p_wcc, curr_comm, v_degree,
+                     comm_size, comm_degree, comm_gid, gid_base, n_local,
+                     constant, p_gain, p_gid, p_dense, r_key, r_sum,
+                     target_hub, cw_hub, next_size, next_degree, n_next);
 }
-template void launch_hub_argmax<float>(const int64_t*, const float*,
-                                       const int32_t*, int64_t,
-                                       const int32_t*, int, const double*,
-                                       const int32_t*, const float*,
-                                       const int64_t*, const float*,
-                                       const int64_t*, double, double*,
-                                       int64_t*, int32_t*, int32_t*,
-                                       float*, hipStream_t);
-template void launch_hub_argmax<double>(const int64_t*, const double*,
-                                        const int32_t*, int64_t,
-                                        const int32_t*, int, const double*,
-                                        const int32_t*, const double*,
-                                        const int64_t*, const double*,
-                                        const int64_t*, double, double*,
-                                        int64_t*, int32_t*, int32_t*,
-                                        double*, hipStream_t);
+#define INSTANTIATE_HUB(W)                                                    \
+  template void launch_hub_argmax<W>(                                         \
+      const int32_t*, const W*, const int64_t*, const int32_t*, int,          \
+      const double*, const int32_t*, const W*, const int64_t*, const W*,      \
+      const int64_t*, int64_t, int32_t, double, double*, double*, int64_t*,   \
+      int32_t*, int32_t*, double*, int32_t*, W*, int64_t*, W*, int64_t,       \
+      hipStream_t);
+INSTANTIATE_HUB(float)
+INSTANTIATE_HUB(double)
 
-int hub_argmax_splits() { return ARGMAX_SPLITS; }
+int hub_slices() { return HUB_SLICES; }
 
 template <typename W>
 void launch_row_sum(const int64_t* rowptr, const W* weights, int64_t nv,
@@ -1139,6 +1315,7 @@ template void sort_pairs64<double>(void*, size_t*, const int64_t*, int64_t*,
                                    const double*, double*, int64_t, int,
                                    hipStream_t);
 
+// Sums of equal adjacent keys (coarsening aggregate, after sort_pairs64).
 template <typename W>
 void reduce_by_key64(void* temp, size_t* bytes, const int64_t* keys,
                      const W* vals, int64_t n, int64_t* uniq_out, W* sums_out,
