@@ -335,6 +335,15 @@ def fused_aggregates_supported() -> bool:
     return _hub_segsort_enabled() and not os.environ.get("CUVITE_PROGRESS")
 
 
+def _class_streams_enabled() -> bool:
+    """Run the block classes 4-6 beside the sub classes 0-3 on an auxiliary
+    stream inside the local_move binding (default; s26 step 70.5 -> 59 ms,
+    profiles/round4_class_schedule.md). CUVITE_CLASS_STREAMS=0 restores the
+    serial schedule: all seven class kernels one after another on the
+    calling stream. Read per call."""
+    return os.environ.get("CUVITE_CLASS_STREAMS", "1") not in ("0", "off")
+
+
 def local_move(inp, next_size=None, next_degree=None):
     """HIP local-move iteration (see local_move.MoveInputs for semantics).
     Returns (target dense comm ids [nv], cluster_weight [nv]).
@@ -346,10 +355,14 @@ def local_move(inp, next_size=None, next_degree=None):
     vertices contribute (those are never visited). The inputs' comm_size /
     comm_degree must be other tensors: they are read while these are written.
 
-    Degree classes 0-4 run in the LDS hash-table kernels; hub vertices
+    Degree classes 0-6 run in the LDS hash-table kernels; hub vertices
     (deg > _hub_cut()) go through the rocPRIM segsort pipeline
-    (_hub_moves_sorted),
-    overlapped on separate HIP streams (disjoint vertex sets)."""
+    (_hub_moves_sorted), overlapped on separate HIP streams (disjoint
+    vertex sets). Inside the class binding the block classes 4-6 run on an
+    auxiliary stream beside the sub classes 0-3 and are joined before it
+    returns (CUVITE_CLASS_STREAMS=0: one after another). At world 1 the
+    process thus uses three streams: the caller's, the side stream here and
+    the binding's auxiliary one."""
     ext = _require()
     vlists, hubs64, hdeg = _buckets_for(inp.rowptr)
     dev = inp.rowptr.device
@@ -360,7 +373,8 @@ def local_move(inp, next_size=None, next_degree=None):
         raise RuntimeError("fused aggregates need the rocPRIM hub path and "
                            "the plain schedule (CUVITE_HUB_SEGSORT=0 or "
                            "CUVITE_PROGRESS is set)")
-    kw = dict(_gid_args(inp), next_size=next_size, next_degree=next_degree)
+    kw = dict(_gid_args(inp), next_size=next_size, next_degree=next_degree,
+              class_streams=_class_streams_enabled())
     if os.environ.get("CUVITE_PROGRESS"):
         import sys
         import time

@@ -136,16 +136,48 @@ cuvite::MoveArgs<W> make_args(const at::Tensor& rowptr, const at::Tensor& tails,
       next_size ? next_size->numel() : 0};
 }
 
-// vlists: the 7 LDS degree-class vertex lists (hubs excluded)
-// (int32, padded is NOT required; launchers pad logically by bounds checks in
-// the sub kernels via nlist).
+// Auxiliary stream and fork/join events of local_move, made once per device
+// and kept for the life of the process (a stream pool would hand out a
+// different stream on every call). The events carry no timing. An event may
+// be recorded again by a later call: a wait binds to the record before it.
+struct ClassStream {
+  hipStream_t stream = nullptr;
+  hipEvent_t fork = nullptr, join = nullptr;
+};
+
+ClassStream& class_stream(int device) {
+  static std::vector<ClassStream> per_device(64);
+  TORCH_CHECK(device >= 0 && device < (int)per_device.size(),
+              "device index out of range");
+  ClassStream& cs = per_device[device];
+  if (cs.stream == nullptr) {
+    C10_HIP_CHECK(hipStreamCreateWithFlags(&cs.stream, hipStreamNonBlocking));
+    C10_HIP_CHECK(hipEventCreateWithFlags(&cs.fork, hipEventDisableTiming));
+    C10_HIP_CHECK(hipEventCreateWithFlags(&cs.join, hipEventDisableTiming));
+  }
+  return cs;
+}
+
+// vlists: the 7 LDS degree-class vertex lists (hubs excluded), int32; a sub
+// class list may be padded with -1 (the sub kernels skip those entries).
+//
+// Schedule. The sub classes 0-3 (6 KB of LDS per block, all 32 wave slots
+// of a CU) run on the calling stream. The block classes 4-6 (24-96 KB
+// tables, 24 down to 4 resident waves per CU) want the opposite resource,
+// so with `class_streams` they run beside the sub classes on an auxiliary
+// stream, largest class first, instead of behind them. The auxiliary
+// stream forks from the calling stream after the outputs are initialised
+// and is joined into it before this returns: the outputs (allocated on the
+// calling stream) carry no work pending elsewhere, and the call is correct
+// from any stream. `class_streams = false` is the serial schedule: all
+// seven kernels on the calling stream.
 std::vector<at::Tensor> local_move(
     at::Tensor rowptr, at::Tensor tails, at::Tensor weights,
     at::Tensor curr_comm, at::Tensor v_degree, at::Tensor comm_size,
     at::Tensor comm_degree, at::Tensor comm_gid, double constant,
     std::vector<at::Tensor> vlists, int64_t gid_base, int64_t n_local,
     c10::optional<at::Tensor> next_size,
-    c10::optional<at::Tensor> next_degree) {
+    c10::optional<at::Tensor> next_degree, bool class_streams) {
   CHECK_DEV(rowptr); CHECK_CONT(rowptr);
   CHECK_DEV(tails); CHECK_CONT(tails);
   CHECK_DEV(weights); CHECK_CONT(weights);
@@ -162,12 +194,33 @@ std::vector<at::Tensor> local_move(
   auto cw = at::zeros({nv}, weights.options());
   auto stream = at::hip::getCurrentHIPStream().stream();
 
+  const bool fork = class_streams && (vlists[4].numel() ||
+                                      vlists[5].numel() || vlists[6].numel());
+  ClassStream* cs = nullptr;
+  hipStream_t block_stream = stream;
+  if (fork) {
+    cs = &class_stream(rowptr.get_device());
+    C10_HIP_CHECK(hipEventRecord(cs->fork, stream));
+    C10_HIP_CHECK(hipStreamWaitEvent(cs->stream, cs->fork, 0));
+    block_stream = cs->stream;
+  }
+
   AT_DISPATCH_FLOATING_TYPES(weights.scalar_type(), "local_move", [&] {
     using W = scalar_t;
     auto args = make_args<W>(rowptr, tails, weights, curr_comm, v_degree,
                              comm_size, comm_degree, comm_gid, constant,
                              target, cw, gid_base, n_local, next_size,
                              next_degree);
+    auto block_class = [&](int c) {
+      if (!vlists[c].numel()) return;
+      const int32_t* vl = vlists[c].data_ptr<int32_t>();
+      const int n = (int)vlists[c].numel();
+      if (c == 4) cuvite::launch_block<W, 2048>(vl, n, args, block_stream);
+      if (c == 5) cuvite::launch_block<W, 4096>(vl, n, args, block_stream);
+      if (c == 6) cuvite::launch_block<W, 8192>(vl, n, args, block_stream);
+    };
+    if (fork)
+      for (int c : {6, 5, 4}) block_class(c);
     if (vlists[0].numel())
       cuvite::launch_sub<W, 16, 32>(vlists[0].data_ptr<int32_t>(),
                                     (int)vlists[0].numel(), args, stream);
@@ -180,16 +233,13 @@ std::vector<at::Tensor> local_move(
     if (vlists[3].numel())
       cuvite::launch_sub<W, 64, 1024>(vlists[3].data_ptr<int32_t>(),
                                       (int)vlists[3].numel(), args, stream);
-    if (vlists[4].numel())
-      cuvite::launch_block<W, 2048>(vlists[4].data_ptr<int32_t>(),
-                                    (int)vlists[4].numel(), args, stream);
-    if (vlists[5].numel())
-      cuvite::launch_block<W, 4096>(vlists[5].data_ptr<int32_t>(),
-                                    (int)vlists[5].numel(), args, stream);
-    if (vlists[6].numel())
-      cuvite::launch_block<W, 8192>(vlists[6].data_ptr<int32_t>(),
-                                    (int)vlists[6].numel(), args, stream);
+    if (!fork)
+      for (int c : {4, 5, 6}) block_class(c);
   });
+  if (fork) {
+    C10_HIP_CHECK(hipEventRecord(cs->join, cs->stream));
+    C10_HIP_CHECK(hipStreamWaitEvent(stream, cs->join, 0));
+  }
   C10_HIP_CHECK(hipGetLastError());
   return {target, cw};
 }
@@ -533,7 +583,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("comm_degree"), py::arg("comm_gid"), py::arg("constant"),
         py::arg("vlists"), py::arg("gid_base") = 0, py::arg("n_local") = 0,
         py::arg("next_size") = py::none(),
-        py::arg("next_degree") = py::none());
+        py::arg("next_degree") = py::none(), py::arg("class_streams") = true);
   m.def("modularity_parts", &modularity_parts,
         "fp64 (sum cw, sum degree^2) reduction (HIP)");
   m.def("scatter_add_", &scatter_add_,

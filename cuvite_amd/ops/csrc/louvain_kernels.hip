@@ -40,6 +40,19 @@
 //                                (profiles/hub_pathology_and_s26.md), and
 //                                the sort pipeline beats it anyway.
 //
+// Schedule (local_move binding): classes 0-3 need 6 KB of LDS per block and
+// fill all 32 wave slots of a CU; classes 4-6 are bound by their tables to
+// 24, 12 and 4 resident waves per CU. The two groups run side by side, the
+// block classes on an auxiliary stream (largest first), and share the CUs
+// (s26 step 70.5 -> 59 ms, profiles/round4_class_schedule.md). Measured in
+// the same round and NOT kept, each slower under that schedule: a
+// predicated 4-deep edge loop without the remainder loop (a load under a
+// per-lane condition makes the compiler branch around it and wait for all
+// but one load in flight before every gather), 512- and 1024-thread blocks
+// for classes 5 and 6 (faster only while the classes run one after
+// another), a second auxiliary stream for class 6, and accounting class 0
+// in a pass of its own (the pass alone takes 12.6 ms of atomics).
+//
 // All gain arithmetic is fp64 regardless of the weight dtype so trajectories
 // match the fp64 CPU oracle (tie-break on equal gains -> smaller GLOBAL id).
 // Global ids of locally owned communities are computed, not gathered
