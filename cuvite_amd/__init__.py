@@ -14,6 +14,8 @@ from .graph import Graph, DistGraph, Partition
 from .louvain import louvain, LouvainConfig, LouvainResult
 from .quality import (PartitionQuality, intra_weight_torch,
                       partition_quality)
+from .connectivity import (ConnectivityReport, cc_components_torch,
+                           split_disconnected)
 
 __all__ = [
     "Graph",
@@ -25,5 +27,8 @@ __all__ = [
     "PartitionQuality",
     "partition_quality",
     "intra_weight_torch",
+    "ConnectivityReport",
+    "split_disconnected",
+    "cc_components_torch",
     "__version__",
 ]

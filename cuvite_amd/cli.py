@@ -22,6 +22,7 @@ import time
 import torch
 
 from .compare import compare_communities
+from .connectivity import split_disconnected
 from .generators import (rgg_dist_graph, rmat_dist_graph, karate_graph,
                          lfr_dist_graph)
 from .graph import DistGraph, Graph, Partition
@@ -118,6 +119,18 @@ def build_parser() -> argparse.ArgumentParser:
                     help="after the run, print the exact modularity of the "
                     "returned partition (\"Final modularity\" is the "
                     "convergence estimate)")
+    ap.add_argument("--connectivity", choices=["final", "level"],
+                    default="off",
+                    help="final: split the returned communities into their "
+                    "connected components (never lowers the exact "
+                    "modularity); level: split every phase's communities "
+                    "before coarsening (all communities connected; the "
+                    "exact modularity may end higher or lower)")
+    ap.add_argument("--check-connected", action="store_true",
+                    help="print how many communities of the partition (the "
+                    "returned one, or the one --score-communities reads) "
+                    "are not connected, and into how many components they "
+                    "fall")
     ap.add_argument("--stats", action="store_true",
                     help="print the graph distribution table "
                     "(ref printStats, distgraph.hpp:100-149)")
@@ -200,6 +213,16 @@ def _load_partition_slice(path: str, args, dg: DistGraph) -> torch.Tensor:
     return inv[dg.base:dg.bound].to(dg.g.device)
 
 
+def _print_connectivity(dg: DistGraph, labels: torch.Tensor, comm: Comm,
+                        backend: str):
+    """The --check-connected line for `labels` on `dg` (collective)."""
+    rep = split_disconnected(dg, labels, comm, backend=backend)
+    if comm.rank == 0:
+        print(f"Connectivity: communities={rep.num_communities} "
+              f"disconnected={rep.num_disconnected} "
+              f"components={rep.num_components}")
+
+
 def write_dist_graph_collect(path: str, dg: DistGraph, comm: Comm):
     """Root-gathers shards and writes one Vite binary (ref writeGraph,
     distgraph.cpp:936-1014; cold path, host-side)."""
@@ -249,14 +272,15 @@ def main(argv=None) -> int:
         return 0
 
     if args.score_communities:
-        pq = partition_quality(
-            dg, _load_partition_slice(args.score_communities, args, dg),
-            comm, backend=args.backend)
+        part_labels = _load_partition_slice(args.score_communities, args, dg)
+        pq = partition_quality(dg, part_labels, comm, backend=args.backend)
         if comm.rank == 0:
             print(f"Partition {args.score_communities}: "
                   f"modularity={pq.modularity:.15g} "
                   f"communities={pq.num_communities} "
                   f"coverage={pq.coverage:.15g}")
+        if args.check_connected:
+            _print_connectivity(dg, part_labels, comm, args.backend)
         return 0
     init_labels = None
     if args.init_communities:
@@ -282,6 +306,7 @@ def main(argv=None) -> int:
         max_colors=max(args.coloring, args.ordering) or 8,
         backend=args.backend,
         verbose=args.verbose,
+        connectivity=args.connectivity,
     )
     if args.max_phases:
         cfg.max_phases = args.max_phases
@@ -334,6 +359,9 @@ def main(argv=None) -> int:
         if comm.rank == 0:
             print(f"Exact modularity: {pq.modularity:.15g} "
                   f"({pq.num_communities} communities)")
+
+    if args.check_connected:
+        _print_connectivity(dg, res.communities, comm, args.backend)
 
     builtin_truth = getattr(args, "_lfr_truth", None)
     if args.output or args.ground_truth or builtin_truth is not None:

@@ -31,6 +31,7 @@ from .halo import (build_halo, exchange_ghost_labels, fetch_comm_info_lists,
 from .local_move import MoveInputs, local_move_torch, modularity_parts
 from .ops import scatter_add_
 from .parallel import Comm
+from .connectivity import ConnectivityReport, split_disconnected
 from .quality import community_aggregates, validate_labels
 from .utils.timers import Timers
 
@@ -54,6 +55,14 @@ class LouvainConfig:
     max_phases: int = TERMINATION_PHASE_COUNT
     max_iters_per_phase: int = 10000
     verbose: bool = False
+    connectivity: str = "off"            # "off" | "final" | "level"
+    #   final: split the returned communities into their connected
+    #     components on the input graph (never lowers the exact modularity)
+    #   level: split every phase's communities on its level graph before
+    #     coarsening, so every coarse vertex and every final community is a
+    #     connected set. Guarantees connectivity only: the phases that follow
+    #     see another graph and the stop test runs on the convergence
+    #     estimate, so the exact modularity may end higher or lower.
 
 
 @dataclass
@@ -68,6 +77,9 @@ class LouvainResult:
     levels: list = field(default_factory=list)  # per-phase {ne_global, iters,
     #   modularity, cluster_s, rebuild_s} — feeds the reference TEPS
     #   definition (teps += ne * iters per phase, main.cpp:448)
+    connectivity: Optional[ConnectivityReport] = None  # "final": the report
+    #   of the split (`communities` are its labels); "level": the report of
+    #   the last phase's split (every level entry carries its own)
 
     @property
     def teps_numerator(self) -> float:
@@ -613,6 +625,18 @@ def louvain(dg: DistGraph, comm: Optional[Comm] = None,
     comm = comm or Comm(dg.g.device)
     cfg = cfg or LouvainConfig()
     dev = dg.g.device
+    if cfg.connectivity not in ("off", "final", "level"):
+        raise ValueError(f"unknown connectivity mode {cfg.connectivity!r}")
+    conn_report = None
+
+    def split_level(cvect, level_halo, entry):
+        # "level": the phase's communities, split on the level graph
+        nonlocal conn_report
+        conn_report = split_disconnected(level, comm=comm, labels=cvect,
+                                         halo=level_halo,
+                                         backend=cfg.backend)
+        entry["connectivity"] = conn_report
+        return conn_report.labels
 
     t_start = time.perf_counter()
     orig_assign = torch.arange(dg.base, dg.bound, device=dev)  # current label of my originals
@@ -660,6 +684,8 @@ def louvain(dg: DistGraph, comm: Optional[Comm] = None,
         levels.append(level_entry)
 
         if (curr_mod - prev_mod) > threshold:
+            if cfg.connectivity == "level":
+                cvect = split_level(cvect, phase_halo, level_entry)
             # compose: originals currently assigned to level vertices; level
             # vertex v now belongs to community cvect[v]
             orig_assign = remap_labels(level, comm, orig_assign, cvect)
@@ -678,11 +704,13 @@ def louvain(dg: DistGraph, comm: Optional[Comm] = None,
             times["rebuild"] += level_entry["rebuild_s"]
         else:
             if cfg.threshold_scaling and not cfg.one_phase and phase < 10:
-                curr_mod2, cvect, iters, _ = run_phase(level, comm, cfg,
-                                                       curr_mod, 1.0e-6)
+                curr_mod2, cvect, iters, phase_halo = run_phase(
+                    level, comm, cfg, curr_mod, 1.0e-6)
                 tot_iters += iters
                 level_entry["iters"] += iters
                 if (curr_mod2 - curr_mod) > 1.0e-6:
+                    if cfg.connectivity == "level":
+                        cvect = split_level(cvect, phase_halo, level_entry)
                     orig_assign = remap_labels(level, comm, orig_assign, cvect)
                     mods.append(curr_mod2)
                     curr_mod = curr_mod2
@@ -696,7 +724,15 @@ def louvain(dg: DistGraph, comm: Optional[Comm] = None,
         if phase >= cfg.max_phases or tot_iters > MAX_TOTAL_ITERS:
             break
 
+    if cfg.connectivity == "final":
+        # on the INPUT graph; its halo is still there only if no coarsening
+        # took it over
+        conn_report = split_disconnected(
+            dg, orig_assign, comm, halo=phase_halo if level is dg else None,
+            backend=cfg.backend)
+        orig_assign = conn_report.labels
+
     times["total"] = time.perf_counter() - t_start
     final_mod = mods[-1] if mods else max(prev_mod, curr_mod)
     return LouvainResult(final_mod, orig_assign, phase + 1, tot_iters,
-                         times, mods, levels)
+                         times, mods, levels, conn_report)

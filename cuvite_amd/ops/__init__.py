@@ -468,6 +468,19 @@ def intra_weight_span() -> int:
     return int(_require().intra_weight_span())
 
 
+def cc_components(rowptr: torch.Tensor, tails_dense: torch.Tensor,
+                  labels_all: torch.Tensor):
+    """Connected components of the graph restricted to edges whose endpoints
+    carry the same label, over the dense node space [0, nv + ng) of
+    halo.tails_dense (locals first, then ghosts; labels int32 or int64).
+    Returns (comp int32 [nv + ng], rounds): comp[x] is the smallest dense id
+    in x's component, rounds the number of hook + compress rounds (one host
+    sync each; 0 when there is no edge or no vertex). HIP kernels on the
+    current stream; the oracle is connectivity.cc_components_torch."""
+    comp, rounds = _require().cc_components(rowptr, tails_dense, labels_all)
+    return comp, int(rounds)
+
+
 def scatter_add_(out: torch.Tensor, idx: torch.Tensor,
                  val: torch.Tensor) -> torch.Tensor:
     """out[idx[i]] += val[i]. On GPU float tensors this MUST go through the

@@ -5,6 +5,7 @@
 #include <c10/hip/HIPStream.h>
 
 #include <cstdint>
+#include <tuple>
 #include <vector>
 
 namespace cuvite {
@@ -78,6 +79,10 @@ template <typename W, typename L>
 void launch_intra_weight(const int64_t*, const int32_t*, const W*, const L*,
                          int64_t, int64_t, int64_t, W*, hipStream_t);
 int intra_weight_span();
+template <typename L>
+void launch_cc_hook(const int64_t*, const int32_t*, const L*, int64_t,
+                    int64_t, int64_t, int32_t*, int32_t*, hipStream_t);
+void launch_cc_compress(int32_t*, int64_t, hipStream_t);
 
 }  // namespace cuvite
 
@@ -573,6 +578,55 @@ at::Tensor intra_weight(at::Tensor rowptr, at::Tensor tails,
   return out;
 }
 
+// Connected components of the graph restricted to edges whose endpoints
+// carry the same label (see cc_hook_kernel): hook, compress and one read of
+// the flag per round, until a hook pass sees no edge between two roots.
+// labels: int32 or int64, [nv + ng]. Returns (comp int32 [nv + ng], rounds).
+std::tuple<at::Tensor, int64_t> cc_components(at::Tensor rowptr,
+                                              at::Tensor tails,
+                                              at::Tensor labels) {
+  CHECK_DEV(rowptr); CHECK_CONT(rowptr);
+  CHECK_DEV(tails); CHECK_CONT(tails);
+  CHECK_DEV(labels); CHECK_CONT(labels);
+  TORCH_CHECK(rowptr.scalar_type() == at::kLong, "rowptr must be int64");
+  TORCH_CHECK(rowptr.numel() >= 1, "rowptr must have nv + 1 entries");
+  TORCH_CHECK(tails.scalar_type() == at::kInt, "tails must be int32");
+  TORCH_CHECK(labels.scalar_type() == at::kInt ||
+              labels.scalar_type() == at::kLong,
+              "labels must be int32 or int64");
+  const int64_t nv = rowptr.numel() - 1;
+  const int64_t ne = tails.numel();
+  const int64_t nl = labels.numel();
+  TORCH_CHECK(nl >= nv, "labels must cover all local vertices");
+  TORCH_CHECK(nl < (int64_t)INT32_MAX,
+              "nv + ng exceeds the int32 dense id range");
+  auto comp = at::arange(nl, tails.options());
+  if (nv == 0 || ne == 0) return {comp, 0};
+  auto changed = at::zeros({1}, tails.options());
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  int64_t rounds = 0;
+  while (true) {
+    TORCH_CHECK(rounds <= nl, "cc_components: no fixed point after ", rounds,
+                " rounds (every changing round removes a root)");
+    rounds++;
+    changed.zero_();
+    if (labels.scalar_type() == at::kInt)
+      cuvite::launch_cc_hook<int32_t>(
+          rowptr.data_ptr<int64_t>(), tails.data_ptr<int32_t>(),
+          labels.data_ptr<int32_t>(), nv, ne, nl, comp.data_ptr<int32_t>(),
+          changed.data_ptr<int32_t>(), stream);
+    else
+      cuvite::launch_cc_hook<int64_t>(
+          rowptr.data_ptr<int64_t>(), tails.data_ptr<int32_t>(),
+          labels.data_ptr<int64_t>(), nv, ne, nl, comp.data_ptr<int32_t>(),
+          changed.data_ptr<int32_t>(), stream);
+    cuvite::launch_cc_compress(comp.data_ptr<int32_t>(), nl, stream);
+    C10_HIP_CHECK(hipGetLastError());
+    if (changed.item<int32_t>() == 0) break;  // the round's one host sync
+  }
+  return {comp, rounds};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -604,6 +658,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "per-vertex weight into the own community, edge-balanced (HIP)");
   m.def("intra_weight_span", &cuvite::intra_weight_span,
         "edges per wave span of the intra_weight kernel");
+  m.def("cc_components", &cc_components,
+        "connected components over same-label edges, hook + compress rounds "
+        "(HIP); returns (comp, rounds)");
   m.def("hub_slices", &cuvite::hub_slices,
         "element slices per hub segment in the hub argmax kernels");
   m.def("hub_moves", &hub_moves,

@@ -734,6 +734,136 @@ __global__ __launch_bounds__(BLOCK) void intra_weight_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// Connected components of the graph restricted to edges whose endpoints
+// carry the same label (is a community connected? split it if not). Nodes
+// are the dense ids [0, nl): local vertices first, then ghosts. The result
+// comp[x] is the smallest dense id in x's component.
+//
+// Hook-and-compress rounds with a monotone min, driven by the host:
+//   hook      every intra edge (u, t) reads ru = comp[u], rt = comp[t] and,
+//             if they differ, does atomicMin(&comp[max], min) and raises
+//             `changed`;
+//   compress  every node chases comp to its root (comp[r] == r) and stores
+//             it;
+// until a hook pass raises no flag. Entering a hook pass comp is fully
+// compressed, so every value in it is a root of that moment, and so is
+// everything a pass writes: only roots are ever hooked, always under a
+// smaller root of the same component. A root hooked twice in one pass keeps
+// the smaller parent only; the edge behind the lost link sees two roots
+// again next round, which is why the flag means "some intra edge saw two
+// roots" and not "an atomicMin lowered something". When no edge raises it,
+// comp is constant on every component, and since comp[x] <= x that constant
+// is the component's smallest id.
+//
+// What makes this safe to run beside other work:
+//   - comp[x] <= x holds at all times (it starts as x and only atomicMin
+//     with a smaller value or a store of x's root ever writes it), so every
+//     device loop walks strictly decreasing indices and ends after at most
+//     x steps whatever other waves write meanwhile;
+//   - no spin-wait, no CAS retry loop, no protocol between workgroups;
+//   - a stale plain read of comp inside the hook pass (another XCD's L2
+//     holds the fresh value) returns an older root of the same component: it
+//     can only postpone a merge by a round, never merge two components;
+//   - coherence between rounds comes from the kernel boundary.
+// Every changing round removes at least one root, so nl + 1 rounds bound
+// the host loop; real graphs take a handful.
+//
+// cc_hook_kernel is intra_weight_kernel's edge pass without the sums: each
+// wave owns IW_SPAN consecutive edges, finds the span's row range with
+// row_of_edge plus the gallop and every lane's row by a binary search
+// inside it, keeps IW_PIPE chunks of loads in flight, and treats a tail
+// outside the label array as matching nothing. No segmented scan and no
+// per-row output.
+// ---------------------------------------------------------------------------
+
+template <typename L, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void cc_hook_kernel(
+    const int64_t* __restrict__ rowptr, const int32_t* __restrict__ tails,
+    const L* __restrict__ labels, int64_t nv, int64_t ne, int64_t nl,
+    int32_t* comp, int32_t* changed) {
+  constexpr int WAVES = BLOCK / 64;
+  const int lane = threadIdx.x % 64;
+  const int64_t nspan = (ne + IW_SPAN - 1) / IW_SPAN;
+  const int64_t sstride = (int64_t)gridDim.x * WAVES;
+  bool saw = false;
+  for (int64_t s = (int64_t)blockIdx.x * WAVES + threadIdx.x / 64; s < nspan;
+       s += sstride) {
+    const int64_t s0 = s * IW_SPAN;
+    const int64_t s1 = (s0 + IW_SPAN < ne) ? s0 + IW_SPAN : ne;
+    // wave-uniform row range of the span
+    int64_t rlo = row_of_edge(rowptr, 0, nv - 1, s0);
+    int64_t rhi = rlo, step = 1;
+    while (rhi + step < nv && rowptr[rhi + step] < s1) {
+      rhi += step;
+      step <<= 1;
+    }
+    rhi = (rhi + step - 1 < nv - 1) ? rhi + step - 1 : nv - 1;
+
+    for (int64_t c = s0; c < s1; c += (int64_t)IW_PIPE * 64) {
+      int32_t t[IW_PIPE];
+#pragma unroll
+      for (int k = 0; k < IW_PIPE; k++) {
+        const int64_t e = c + k * 64 + lane;
+        t[k] = (e < s1) ? tails[e] : -1;  // -1 fails the guard below
+      }
+      L lt[IW_PIPE];
+      bool inb[IW_PIPE];
+#pragma unroll
+      for (int k = 0; k < IW_PIPE; k++) {
+        // memory-safety guard: a tail outside the label array matches nothing
+        inb[k] = (uint64_t)(int64_t)t[k] < (uint64_t)nl;
+        lt[k] = inb[k] ? labels[t[k]] : (L)0;
+      }
+#pragma unroll
+      for (int k = 0; k < IW_PIPE; k++) {
+        const int64_t cb = c + k * 64;
+        if (cb >= s1) break;  // wave-uniform
+        const int64_t e = cb + lane;
+        int32_t row = -1;
+        if (e < s1) {
+          row = (int32_t)row_of_edge(rowptr, rlo, rhi, e);
+          if (inb[k] && t[k] != row && lt[k] == labels[row]) {
+            const int32_t ru = comp[row], rt = comp[t[k]];
+            if (ru != rt) {
+              atomicMin(&comp[ru > rt ? ru : rt], ru > rt ? rt : ru);
+              saw = true;
+            }
+          }
+        }
+        const int32_t last_row = __shfl(row, 63, 64);
+        if (last_row >= 0) rlo = last_row;
+      }
+    }
+  }
+  if (saw) changed[0] = 1;  // plain vector store; every writer stores 1
+}
+
+// One full chase per node. The chain from x walks strictly decreasing ids,
+// so it ends within x steps; roots are fixed for the whole pass (a root is
+// only ever stored its own id) and a concurrent store of another node's
+// root only shortens the way. Workgroups are dispatched in index order, so
+// even the depth-nl chain a hook pass builds on a path in natural vertex
+// order is mostly met already compressed. The price of doing without
+// pointer-doubling passes (a host sync each) is the worst case: a node whose
+// whole chain is still uncompressed walks it alone, one dependent load per
+// step. On R-MAT the pass takes 12 us at 4 M nodes (profiles/
+// connectivity.md).
+__global__ void cc_compress_kernel(int32_t* comp, int64_t nl) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; x < nl;
+       x += stride) {
+    int32_t r = comp[x];
+    if (r == (int32_t)x) continue;
+    int32_t p = comp[r];
+    while (p < r) {  // p <= r always; equal at the root
+      r = p;
+      p = comp[r];
+    }
+    comp[x] = r;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Hub candidate generation via rocPRIM: gather the neighbours' community
 // ids, then a per-hub segmented radix sort of those keys (only
 // ceil(log2 C) bits) with the edge weights as payload. The torch fallback
@@ -1292,6 +1422,34 @@ INSTANTIATE_IW(double, int32_t)
 INSTANTIATE_IW(double, int64_t)
 
 int intra_weight_span() { return IW_SPAN; }
+
+// One hook pass of the label-restricted connected components (see
+// cc_hook_kernel). The caller zeroes `changed` first and checks nv, ne > 0.
+template <typename L>
+void launch_cc_hook(const int64_t* rowptr, const int32_t* tails,
+                    const L* labels, int64_t nv, int64_t ne, int64_t nl,
+                    int32_t* comp, int32_t* changed, hipStream_t stream) {
+  if (nv == 0 || ne == 0) return;
+  constexpr int BLOCK = 256;
+  const int64_t nspan = (ne + IW_SPAN - 1) / IW_SPAN;
+  hipLaunchKernelGGL((cc_hook_kernel<L, BLOCK>),
+                     dim3(grid_for(nspan * 64, BLOCK)), dim3(BLOCK), 0, stream,
+                     rowptr, tails, labels, nv, ne, nl, comp, changed);
+}
+template void launch_cc_hook<int32_t>(const int64_t*, const int32_t*,
+                                      const int32_t*, int64_t, int64_t,
+                                      int64_t, int32_t*, int32_t*,
+                                      hipStream_t);
+template void launch_cc_hook<int64_t>(const int64_t*, const int32_t*,
+                                      const int64_t*, int64_t, int64_t,
+                                      int64_t, int32_t*, int32_t*,
+                                      hipStream_t);
+
+void launch_cc_compress(int32_t* comp, int64_t nl, hipStream_t stream) {
+  if (nl == 0) return;
+  hipLaunchKernelGGL(cc_compress_kernel, dim3(grid_for(nl, 256)), dim3(256),
+                     0, stream, comp, nl);
+}
 
 // rocPRIM wrappers (two-phase: bytes query with temp==nullptr, then run).
 template <typename W>
