@@ -16,6 +16,7 @@ from .quality import (PartitionQuality, intra_weight_torch,
                       partition_quality)
 from .connectivity import (ConnectivityReport, cc_components_torch,
                            split_disconnected)
+from .refine import RefineReport, refine_coin, refine_partition
 
 __all__ = [
     "Graph",
@@ -30,5 +31,8 @@ __all__ = [
     "ConnectivityReport",
     "split_disconnected",
     "cc_components_torch",
+    "RefineReport",
+    "refine_coin",
+    "refine_partition",
     "__version__",
 ]

@@ -126,6 +126,13 @@ def build_parser() -> argparse.ArgumentParser:
                     "modularity); level: split every phase's communities "
                     "before coarsening (all communities connected; the "
                     "exact modularity may end higher or lower)")
+    ap.add_argument("--leiden", action="store_true",
+                    help="Leiden mode: refine every phase's communities "
+                    "into connected sub-communities before coarsening and "
+                    "start the next phase from the parent communities; the "
+                    "result always passes through the final split "
+                    "(--connectivity final is implied, level is rejected; "
+                    "-p skips refinement)")
     ap.add_argument("--check-connected", action="store_true",
                     help="print how many communities of the partition (the "
                     "returned one, or the one --score-communities reads) "
@@ -142,6 +149,8 @@ def validate(args, world: int):
         sys.exit("Cannot enable both -c and -d")
     if args.one_phase and args.threshold_cycling:
         sys.exit("Cannot enable both -p and -i")
+    if args.leiden and args.connectivity == "level":
+        sys.exit("Cannot enable both --leiden and --connectivity level")
     if args.early_term and not 1 <= args.early_term <= 4:
         sys.exit("-t must be 1..4")
     if args.early_term in (2, 4) and not 0.0 <= args.et_alpha <= 1.0:
@@ -307,6 +316,7 @@ def main(argv=None) -> int:
         backend=args.backend,
         verbose=args.verbose,
         connectivity=args.connectivity,
+        algorithm="leiden" if args.leiden else "louvain",
     )
     if args.max_phases:
         cfg.max_phases = args.max_phases
@@ -330,6 +340,18 @@ def main(argv=None) -> int:
     if comm.rank == 0:
         for lvl, q in enumerate(res.modularity_per_level):
             print(f"Level {lvl}: modularity = {q:.6f}")
+        for lvl, entry in enumerate(res.levels):
+            rep = entry.get("refine")
+            if rep is not None:
+                print(f"Refinement: level={lvl} "
+                      f"communities={rep.num_communities} "
+                      f"subcommunities={rep.num_subcommunities} "
+                      f"rounds={rep.rounds}")
+        if args.leiden and res.connectivity is not None:
+            print(f"Final split: communities="
+                  f"{res.connectivity.num_communities} "
+                  f"disconnected={res.connectivity.num_disconnected} "
+                  f"components={res.connectivity.num_components}")
         # TEPS following the reference definition (main.cpp:448,509) with
         # one fix: the reference multiplies each level's ne by the CUMULATIVE
         # iteration count (inflating later levels); we use the original ne x

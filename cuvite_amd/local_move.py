@@ -195,3 +195,149 @@ def modularity_parts(cluster_weight: torch.Tensor,
     le = cluster_weight.to(torch.float64).sum()
     la2 = (local_comm_degree.to(torch.float64) ** 2).sum()
     return torch.stack([le, la2])
+
+
+# ---------------------------------------------------------------------------
+# Leiden refinement round: the local move with a per-round mover set and a
+# bound filter on the candidates (cuvite_amd/refine.py drives the rounds).
+#
+#   mover_bound  int32 [>= nv]  bound id of local vertex i if it moves this
+#                               round, -1 if it does not
+#   cand_bound   int32 [nc]     bound id of dense community y if it may be
+#                               joined this round, -1 if it may not
+#
+# A mover i takes the candidate y != cc with cand_bound[y] == mover_bound[i]
+# of largest strictly positive gain (same expression as above), ties to the
+# smaller GLOBAL id; there is no singleton-swap guard (the caller's choice of
+# movers and targets rules swaps out). Everyone else, and a mover without
+# edges, keeps its label. cluster_weight is map[cc] for a mover with edges
+# and 0 for everyone else. comm_size is not read.
+# ---------------------------------------------------------------------------
+
+def refine_move_pydict(inp: MoveInputs, mover_bound: torch.Tensor,
+                       cand_bound: torch.Tensor):
+    """Dict-based golden model of one refine round. Slow; tests only."""
+    nv = inp.nv
+    rowptr = inp.rowptr.tolist()
+    tails = inp.tails.tolist()
+    weights = inp.weights.tolist()
+    curr = inp.curr_comm.tolist()
+    vdeg = inp.v_degree.tolist()
+    cdeg = inp.comm_degree.tolist()
+    gid = inp.comm_gid.tolist()
+    mb = mover_bound.tolist()
+    cb = cand_bound.tolist()
+    const = inp.constant
+
+    target = [0] * nv
+    cluster_weight = [0.0] * nv
+    for i in range(nv):
+        cc = curr[i]
+        target[i] = cc
+        e0, e1 = rowptr[i], rowptr[i + 1]
+        if mb[i] < 0 or e0 == e1:
+            continue
+        selfloop = 0.0
+        counter = {cc: 0.0}
+        for k in range(e0, e1):
+            t = tails[k]
+            w = weights[k]
+            if t == i:
+                selfloop += w
+            tc = curr[t]
+            counter[tc] = counter.get(tc, 0.0) + w
+        cluster_weight[i] = counter[cc]
+        eix = counter[cc] - selfloop
+        ax = cdeg[cc] - vdeg[i]
+        max_gain = 0.0
+        max_idx = cc
+        for y, eiy in counter.items():
+            if y == cc or cb[y] != mb[i]:
+                continue
+            gain = 2.0 * (eiy - eix) - 2.0 * vdeg[i] * (cdeg[y] - ax) * const
+            if gain > max_gain or (gain == max_gain and gain != 0.0
+                                   and gid[y] < gid[max_idx]):
+                max_gain = gain
+                max_idx = y
+        target[i] = max_idx
+
+    dev = inp.rowptr.device
+    return (torch.tensor(target, dtype=inp.curr_comm.dtype, device=dev),
+            torch.tensor(cluster_weight, dtype=inp.weights.dtype, device=dev))
+
+
+def refine_move_torch(inp: MoveInputs, mover_bound: torch.Tensor,
+                      cand_bound: torch.Tensor):
+    """Vectorized twin of refine_move_pydict (the CPU path and the reference
+    the HIP refine kernels are tested against). Only the movers' rows are
+    expanded, so a late round with few movers costs little.
+
+    Returns (target [nv] dense comm ids, cluster_weight [nv])."""
+    nv = inp.nv
+    dev = inp.rowptr.device
+    W = inp.weights.dtype
+    cc_all = inp.curr_comm.to(torch.int64)
+    target = cc_all[:nv].clone()
+    cluster_weight = torch.zeros(nv, dtype=W, device=dev)
+    mb_all = mover_bound[:nv].to(torch.int64)
+    deg = inp.rowptr[1:] - inp.rowptr[:-1]
+    movers = ((mb_all >= 0) & (deg > 0)).nonzero(as_tuple=True)[0]
+    if movers.numel() == 0:
+        return target.to(inp.curr_comm.dtype), cluster_weight
+
+    mdeg = deg[movers]
+    m = movers.numel()
+    offs = torch.zeros(m + 1, dtype=torch.int64, device=dev)
+    offs[1:] = torch.cumsum(mdeg, dim=0)
+    seg = torch.repeat_interleave(torch.arange(m, device=dev), mdeg)
+    eidx = inp.rowptr[movers][seg] + (
+        torch.arange(int(offs[-1]), device=dev) - offs[seg])
+    tails = inp.tails[eidx].to(torch.int64)
+    wts = inp.weights[eidx]
+    tcomm = cc_all[tails]
+
+    selfloop = torch.zeros(m, dtype=W, device=dev)
+    self_mask = tails == movers[seg]
+    if bool(self_mask.any()):
+        selfloop.index_add_(0, seg[self_mask], wts[self_mask])
+
+    nc = inp.comm_degree.numel()
+    key_s, order = torch.sort(seg * nc + tcomm)
+    w_s = wts[order]
+    uniq, inv = torch.unique_consecutive(key_s, return_inverse=True)
+    gsum = torch.zeros(uniq.numel(), dtype=W, device=dev)
+    gsum.index_add_(0, inv, w_s)
+    gv = uniq // nc     # mover index of each group
+    gc = uniq % nc      # community of each group
+
+    cc = cc_all[movers]
+    own = gc == cc[gv]
+    cw_m = torch.zeros(m, dtype=W, device=dev)
+    cw_m[gv[own]] = gsum[own]
+    cluster_weight[movers] = cw_m
+
+    vdeg = inp.v_degree[movers]
+    eix = cw_m - selfloop
+    ax = inp.comm_degree[cc] - vdeg
+
+    cand = ~own & (cand_bound.to(torch.int64)[gc] == mb_all[movers][gv])
+    cv, cy, eiy = gv[cand], gc[cand], gsum[cand]
+    if cv.numel() == 0:
+        return target.to(inp.curr_comm.dtype), cluster_weight
+    # gain arithmetic in fp64, expression and operand order of
+    # local_move_torch
+    gain = (2.0 * (eiy.to(torch.float64) - eix[cv].to(torch.float64))
+            - 2.0 * vdeg[cv].to(torch.float64)
+            * (inp.comm_degree[cy].to(torch.float64)
+               - ax[cv].to(torch.float64)) * inp.constant)
+    gidy = inp.comm_gid[cy]
+    o1 = torch.argsort(gidy, stable=True)
+    o2 = o1[torch.argsort(-gain[o1], stable=True)]
+    o3 = o2[torch.argsort(cv[o2], stable=True)]
+    cv3 = cv[o3]
+    first = torch.ones_like(cv3, dtype=torch.bool)
+    first[1:] = cv3[1:] != cv3[:-1]
+    sel = o3[first]
+    pos = gain[sel] > 0
+    target[movers[cv[sel][pos]]] = cy[sel][pos]
+    return target.to(inp.curr_comm.dtype), cluster_weight

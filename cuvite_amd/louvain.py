@@ -33,6 +33,7 @@ from .ops import scatter_add_
 from .parallel import Comm
 from .connectivity import ConnectivityReport, split_disconnected
 from .quality import community_aggregates, validate_labels
+from .refine import REFINE_MAX_ROUNDS, refine_partition
 from .utils.timers import Timers
 
 TERMINATION_PHASE_COUNT = 200   # ref utils.hpp:17-19
@@ -63,6 +64,17 @@ class LouvainConfig:
     #     connected set. Guarantees connectivity only: the phases that follow
     #     see another graph and the stop test runs on the convergence
     #     estimate, so the exact modularity may end higher or lower.
+    algorithm: str = "louvain"           # "louvain" | "leiden"
+    #   leiden: after every local-moving phase that passes the gain test the
+    #     phase's communities are refined into connected sub-communities
+    #     (refine.refine_partition), the level graph is coarsened by those,
+    #     and the next phase starts from the parent communities. The result
+    #     always passes through the final split (connectivity="final" is
+    #     implied; "level" is rejected). -p skips refinement; coloring,
+    #     ordering and early termination apply to the local-moving phases
+    #     only.
+    refine_max_rounds: int = REFINE_MAX_ROUNDS
+    refine_seed: int = 0
 
 
 @dataclass
@@ -76,7 +88,9 @@ class LouvainResult:
     modularity_per_level: list = field(default_factory=list)
     levels: list = field(default_factory=list)  # per-phase {ne_global, iters,
     #   modularity, cluster_s, rebuild_s} — feeds the reference TEPS
-    #   definition (teps += ne * iters per phase, main.cpp:448)
+    #   definition (teps += ne * iters per phase, main.cpp:448); under
+    #   algorithm="leiden" a refined level also carries "refine", its
+    #   RefineReport
     connectivity: Optional[ConnectivityReport] = None  # "final": the report
     #   of the split (`communities` are its labels); "level": the report of
     #   the last phase's split (every level entry carries its own)
@@ -607,6 +621,42 @@ def _modularity(state: PhaseState) -> float:
     return float(parts[0]) * c - float(parts[1]) * c * c
 
 
+def _refined_init_labels(level: DistGraph, comm: Comm, cvect: torch.Tensor,
+                         sub: torch.Tensor, renum) -> torch.Tensor:
+    """Start labels for the phase after a refined level: int64, one per new
+    local vertex. New vertex i is the i-th surviving sub-community this rank
+    owns (sub s is owned by the owner of vertex s, which is in it and knows
+    its community cvect[s]); its label is the smallest new vertex id among
+    the subs of that community: a scatter-amin at the community's owner and
+    a lookup back. Collective (`renum` is coarsen's)."""
+    from .coarsen import _owner_lookup
+    dev = cvect.device
+    base, nv = level.base, level.nv
+    gids = torch.arange(base, level.bound, device=dev)
+    surv = (sub == gids).nonzero(as_tuple=True)[0]
+    new_ids = renum(gids[surv])
+    c_of_new = cvect[surv]
+    big = torch.iinfo(torch.int64).max
+    lab = torch.full((nv,), big, dtype=torch.int64, device=dev)
+    if comm.world == 1:
+        lab.scatter_reduce_(0, c_of_new - base, new_ids, reduce="amin")
+        return lab[c_of_new - base]
+    order = torch.argsort(c_of_new)
+    cs, ns = c_of_new[order], new_ids[order]
+    offs = torch.searchsorted(cs, level.partition.parts.to(dev))
+    world = comm.world
+    got_c = comm.all_to_all_v([cs[offs[p]:offs[p + 1]] for p in range(world)])
+    got_n = comm.all_to_all_v([ns[offs[p]:offs[p + 1]] for p in range(world)],
+                              recv_counts=[int(g.numel()) for g in got_c])
+    for gc, gn in zip(got_c, got_n):
+        if gc.numel():
+            lab.scatter_reduce_(0, gc - base, gn, reduce="amin")
+    uniq_c = torch.unique(c_of_new)  # sorted
+    vals = _owner_lookup(comm, level.partition, uniq_c,
+                         lambda g: lab[g - base])
+    return vals[torch.searchsorted(uniq_c, c_of_new)]
+
+
 def louvain(dg: DistGraph, comm: Optional[Comm] = None,
             cfg: Optional[LouvainConfig] = None,
             halo=None,
@@ -627,6 +677,12 @@ def louvain(dg: DistGraph, comm: Optional[Comm] = None,
     dev = dg.g.device
     if cfg.connectivity not in ("off", "final", "level"):
         raise ValueError(f"unknown connectivity mode {cfg.connectivity!r}")
+    if cfg.algorithm not in ("louvain", "leiden"):
+        raise ValueError(f"unknown algorithm {cfg.algorithm!r}")
+    leiden = cfg.algorithm == "leiden"
+    if leiden and cfg.connectivity == "level":
+        raise ValueError("algorithm='leiden' refines every level itself; "
+                         "connectivity='level' cannot be combined with it")
     conn_report = None
 
     def split_level(cvect, level_halo, entry):
@@ -640,6 +696,11 @@ def louvain(dg: DistGraph, comm: Optional[Comm] = None,
 
     t_start = time.perf_counter()
     orig_assign = torch.arange(dg.base, dg.bound, device=dev)  # current label of my originals
+    # leiden: the level vertex every original sits in (under louvain that is
+    # orig_assign itself, communities become the next vertices), and the
+    # start labels of the next phase (the parent communities)
+    orig_vertex = orig_assign
+    next_init = None
     prev_mod, curr_mod = -1.0, -1.0
     phase = 0
     short_phase = 0
@@ -673,7 +734,7 @@ def louvain(dg: DistGraph, comm: Optional[Comm] = None,
         curr_mod, cvect, iters, phase_halo = run_phase(
             level, comm, cfg, curr_mod, threshold,
             colors=colors, num_colors=num_colors, halo=pre_halo,
-            init_labels=init_labels if phase == 0 else None)
+            init_labels=init_labels if phase == 0 else next_init)
         pre_halo = None
         t_cluster = time.perf_counter() - t0
         times["clustering"] += t_cluster
@@ -688,30 +749,55 @@ def louvain(dg: DistGraph, comm: Optional[Comm] = None,
                 cvect = split_level(cvect, phase_halo, level_entry)
             # compose: originals currently assigned to level vertices; level
             # vertex v now belongs to community cvect[v]
-            orig_assign = remap_labels(level, comm, orig_assign, cvect)
+            orig_assign = remap_labels(level, comm, orig_vertex if leiden
+                                       else orig_assign, cvect)
             mods.append(curr_mod)
             if cfg.one_phase:
                 break
             t0 = time.perf_counter()
+            if leiden:
+                # refine the communities into connected subs (the phase's
+                # hub caches still fit: same level graph), coarsen by the
+                # subs, start the next phase from the parent communities
+                rep = refine_partition(
+                    level, cvect, comm, halo=phase_halo, backend=cfg.backend,
+                    max_rounds=cfg.refine_max_rounds, seed=cfg.refine_seed,
+                    level=phase)
+                level_entry["refine"] = rep
+                orig_vertex = remap_labels(level, comm, orig_vertex,
+                                           rep.labels)
             if dev.type == "cuda":
                 from . import ops
                 ops.clear_phase_caches()  # free phase-keyed GPU tensors
-            level, renum = coarsen(level, comm, cvect, halo=phase_halo)
+            if leiden:
+                new_level, renum = coarsen(level, comm, rep.labels,
+                                           halo=phase_halo)
+                orig_vertex = renum(orig_vertex)
+                next_init = _refined_init_labels(level, comm, cvect,
+                                                 rep.labels, renum)
+                level = new_level
+                # orig_assign keeps this level's community gids (all below
+                # nv_global): they are the result if no later phase gains
+            else:
+                level, renum = coarsen(level, comm, cvect, halo=phase_halo)
+                # cvect-composed orig_assign holds OLD comm gids; renumber
+                orig_assign = renum(orig_assign)
             phase_halo = None  # free the ghost structure before next phase
-            # cvect-composed orig_assign holds OLD comm gids; renumber them
-            orig_assign = renum(orig_assign)
             level_entry["rebuild_s"] = time.perf_counter() - t0
             times["rebuild"] += level_entry["rebuild_s"]
         else:
             if cfg.threshold_scaling and not cfg.one_phase and phase < 10:
                 curr_mod2, cvect, iters, phase_halo = run_phase(
-                    level, comm, cfg, curr_mod, 1.0e-6)
+                    level, comm, cfg, curr_mod, 1.0e-6,
+                    init_labels=next_init if phase > 0 else None)
                 tot_iters += iters
                 level_entry["iters"] += iters
                 if (curr_mod2 - curr_mod) > 1.0e-6:
                     if cfg.connectivity == "level":
                         cvect = split_level(cvect, phase_halo, level_entry)
-                    orig_assign = remap_labels(level, comm, orig_assign, cvect)
+                    orig_assign = remap_labels(
+                        level, comm, orig_vertex if leiden else orig_assign,
+                        cvect)
                     mods.append(curr_mod2)
                     curr_mod = curr_mod2
             break
@@ -724,7 +810,7 @@ def louvain(dg: DistGraph, comm: Optional[Comm] = None,
         if phase >= cfg.max_phases or tot_iters > MAX_TOTAL_ITERS:
             break
 
-    if cfg.connectivity == "final":
+    if cfg.connectivity == "final" or leiden:
         # on the INPUT graph; its halo is still there only if no coarsening
         # took it over
         conn_report = split_disconnected(

@@ -151,20 +151,22 @@ def _gid_args(inp) -> dict:
     return dict(gid_base=int(base), n_local=int(inp.nv))
 
 
-def _hub_moves_sorted(inp, hubs, hdeg, nxt=None):
+def _hub_moves_sorted(inp, hubs, hdeg, nxt=None, bounds=None):
     """Chunk wrapper: split the hub list into phase-static groups whose edge
     totals stay under the torch sort cap; each hub's candidates are
     independent. Returns (target_dense int32 [nhub], wcc [nhub]) aligned
     with `hubs`. `nxt`: optional (next_size, next_degree) pair; every group's
-    hub_moves call accounts its own hubs in it."""
+    hub_moves call accounts its own hubs in it. `bounds`: optional
+    (mover_bound, cand_bound) pair of a refine round (see refine_move)."""
     groups = _hub_groups(inp, hubs, hdeg)
     if len(groups) == 1:
-        return _hub_moves_sorted_one(inp, groups[0][0], groups[0][1], nxt)
+        return _hub_moves_sorted_one(inp, groups[0][0], groups[0][1], nxt,
+                                     bounds)
     tgt = torch.empty(hubs.numel(), dtype=torch.int32, device=hubs.device)
     wcc = torch.empty(hubs.numel(), dtype=inp.weights.dtype,
                       device=hubs.device)
     for hubs_g, hdeg_g, m in groups:
-        t, w = _hub_moves_sorted_one(inp, hubs_g, hdeg_g, nxt)
+        t, w = _hub_moves_sorted_one(inp, hubs_g, hdeg_g, nxt, bounds)
         tgt[m] = t
         wcc[m] = w
     return tgt, wcc
@@ -246,7 +248,7 @@ def _hub_static(inp, hubs, hdeg):
     return data
 
 
-def _hub_moves_sorted_one(inp, hubs, hdeg, nxt=None):
+def _hub_moves_sorted_one(inp, hubs, hdeg, nxt=None, bounds=None):
     """Hub vertices (deg > hub cut, default 6144) via radix sort +
     segmented reduction.
     Default path: the fully-device rocPRIM pipeline (hub_moves binding).
@@ -265,6 +267,12 @@ def _hub_moves_sorted_one(inp, hubs, hdeg, nxt=None):
         # then one sliced pass over the sorted pairs for run sums, gains
         # and argmax (no host sync per iteration)
         tails32, offs, wts_w, hubs32 = extra
+        if bounds is not None:
+            tgt_hub, cw_hub = _require().hub_refine_moves(
+                tails32, wts_w, offs, hubs32, selfloop,
+                inp.curr_comm, inp.v_degree, inp.comm_degree, inp.comm_gid,
+                float(inp.constant), bounds[0], bounds[1], **_gid_args(inp))
+            return tgt_hub, cw_hub
         tgt_hub, cw_hub = _require().hub_moves(
             tails32, wts_w, offs, hubs32, selfloop,
             inp.curr_comm, inp.v_degree, inp.comm_size, inp.comm_degree,
@@ -309,6 +317,13 @@ def _hub_moves_sorted_one(inp, hubs, hdeg, nxt=None):
         (ay - ax[hub_of]) * float(inp.constant)
     g = torch.where(is_cc, torch.full_like(g, -torch.inf), g)
     del ay, wsum
+    if bounds is not None:
+        # refine round: only candidates with the mover's bound count, and a
+        # hub that does not move has none
+        mb = bounds[0][hubs].to(torch.int64)
+        ok = (mb[hub_of] >= 0) & (bounds[1].to(torch.int64)[y] == mb[hub_of])
+        g = torch.where(ok, g, torch.full_like(g, -torch.inf))
+        wcc = torch.where(mb >= 0, wcc, torch.zeros_like(wcc))
 
     gmax = torch.full((nhub,), 0.0, dtype=torch.float64, device=dev)
     gmax.scatter_reduce_(0, hub_of, g, reduce="amax")
@@ -321,6 +336,8 @@ def _hub_moves_sorted_one(inp, hubs, hdeg, nxt=None):
     final = winner & (gid_y == gid_win[hub_of])
     tgt_dense = cc.clone()
     tgt_dense[hub_of[final]] = y[final]
+    if bounds is not None:
+        return tgt_dense.to(torch.int32), wcc.to(inp.weights.dtype)
     # singleton-swap guard (louvain.cpp:2238-2239)
     guard = (inp.comm_size[tgt_dense] == 1) & (inp.comm_size[cc] == 1) & \
         (inp.comm_gid[tgt_dense] > inp.comm_gid[cc])
@@ -440,6 +457,61 @@ def local_move(inp, next_size=None, next_degree=None):
         vlists, **kw)
     if run_hub_sort:
         hub_tgt, hub_cw = _hub_moves_sorted(inp, hubs64, hdeg, nxt)
+        target[hubs64] = hub_tgt
+        cw[hubs64] = hub_cw
+    return target, cw
+
+
+def refine_move(inp, mover_bound: torch.Tensor, cand_bound: torch.Tensor,
+                out=None):
+    """HIP Leiden refine round (semantics: local_move.refine_move_torch).
+    `mover_bound` int32 [>= nv]: bound id of a vertex that moves this round,
+    else -1; `cand_bound` int32 [nc]: bound id of a dense community that may
+    be joined this round, else -1. Returns (target dense comm ids [nv],
+    cluster_weight [nv]); a vertex that does not move keeps its label.
+
+    Same routing as local_move: the refine variants of the degree-class
+    kernels, and the hub pipeline with the refine argmax kernels. The hub
+    adjacency is cached per phase for the full hub list, so the sort covers
+    every hub whenever one of them moves (non-movers leave the argmax
+    kernels at once); a round in which no hub moves skips the hub pipeline,
+    at the price of one host sync. inp.comm_size is not read. `out`: optional
+    (target int32 [nv], cluster_weight [nv]) pair of contiguous buffers to
+    write the result into."""
+    ext = _require()
+    vlists, hubs64, hdeg = _buckets_for(inp.rowptr)
+    dev = inp.rowptr.device
+    kw = dict(_gid_args(inp), class_streams=_class_streams_enabled())
+    run_hub_sort = hubs64.numel() > 0 and bool(
+        (mover_bound[hubs64] >= 0).any())
+
+    def classes():
+        return ext.refine_move_bucketed(
+            inp.rowptr, inp.tails, inp.weights, inp.curr_comm, inp.v_degree,
+            inp.comm_degree, inp.comm_gid, float(inp.constant), vlists,
+            mover_bound, cand_bound, **kw,
+            out_target=None if out is None else out[0],
+            out_cw=None if out is None else out[1])
+
+    bounds = (mover_bound, cand_bound)
+    if run_hub_sort and not os.environ.get("CUVITE_NO_OVERLAP"):
+        # as in local_move: class kernels on the side stream beside the hub
+        # pipeline, hub results scattered after the join
+        main = torch.cuda.current_stream(dev)
+        side = _side_stream(dev)
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            target, cw = classes()
+        hub_tgt, hub_cw = _hub_moves_sorted(inp, hubs64, hdeg, None, bounds)
+        main.wait_stream(side)
+        target.record_stream(main)
+        cw.record_stream(main)
+        target[hubs64] = hub_tgt
+        cw[hubs64] = hub_cw
+        return target, cw
+    target, cw = classes()
+    if run_hub_sort:
+        hub_tgt, hub_cw = _hub_moves_sorted(inp, hubs64, hdeg, None, bounds)
         target[hubs64] = hub_tgt
         cw[hubs64] = hub_cw
     return target, cw

@@ -34,6 +34,12 @@ template <typename W, int LANES, int CAP>
 void launch_sub(const int32_t*, int, const MoveArgs<W>&, hipStream_t);
 template <typename W, int CAP>
 void launch_block(const int32_t*, int, const MoveArgs<W>&, hipStream_t);
+template <typename W, int LANES, int CAP>
+void launch_refine_sub(const int32_t*, int, const MoveArgs<W>&,
+                       const int32_t*, const int32_t*, hipStream_t);
+template <typename W, int CAP>
+void launch_refine_block(const int32_t*, int, const MoveArgs<W>&,
+                         const int32_t*, const int32_t*, hipStream_t);
 template <typename W>
 void launch_modularity(const W*, const W*, int64_t, double*, hipStream_t);
 template <typename W>
@@ -64,6 +70,14 @@ void launch_hub_argmax(const int32_t*, const W*, const int64_t*,
                        int64_t, int32_t, double, double*, double*, int64_t*,
                        int32_t*, int32_t*, double*, int32_t*, W*, int64_t*,
                        W*, int64_t, hipStream_t);
+template <typename W>
+void launch_hub_refine_argmax(const int32_t*, const W*, const int64_t*,
+                              const int32_t*, int, const double*,
+                              const int32_t*, const W*, const W*,
+                              const int64_t*, int64_t, int32_t, double,
+                              double*, double*, int64_t*, int32_t*, int32_t*,
+                              double*, int32_t*, W*, const int32_t*,
+                              const int32_t*, hipStream_t);
 int hub_slices();
 template <typename W>
 void launch_apply_deltas(const int64_t*, const int64_t*, const W*, int64_t,
@@ -176,13 +190,20 @@ ClassStream& class_stream(int device) {
 // calling stream) carry no work pending elsewhere, and the call is correct
 // from any stream. `class_streams = false` is the serial schedule: all
 // seven kernels on the calling stream.
-std::vector<at::Tensor> local_move(
+//
+// With `mover_bound` / `cand_bound` (both or neither) the refine kernels run
+// instead: see refine_move below.
+std::vector<at::Tensor> local_move_impl(
     at::Tensor rowptr, at::Tensor tails, at::Tensor weights,
     at::Tensor curr_comm, at::Tensor v_degree, at::Tensor comm_size,
     at::Tensor comm_degree, at::Tensor comm_gid, double constant,
     std::vector<at::Tensor> vlists, int64_t gid_base, int64_t n_local,
     c10::optional<at::Tensor> next_size,
-    c10::optional<at::Tensor> next_degree, bool class_streams) {
+    c10::optional<at::Tensor> next_degree, bool class_streams,
+    const int32_t* mover_bound, const int32_t* cand_bound,
+    c10::optional<at::Tensor> out_target = c10::nullopt,
+    c10::optional<at::Tensor> out_cw = c10::nullopt) {
+  const bool refine = mover_bound != nullptr;
   CHECK_DEV(rowptr); CHECK_CONT(rowptr);
   CHECK_DEV(tails); CHECK_CONT(tails);
   CHECK_DEV(weights); CHECK_CONT(weights);
@@ -195,8 +216,26 @@ std::vector<at::Tensor> local_move(
   check_next(next_size, next_degree, weights);
 
   const int64_t nv = rowptr.numel() - 1;
-  auto target = curr_comm.narrow(0, 0, nv).clone();
-  auto cw = at::zeros({nv}, weights.options());
+  TORCH_CHECK(out_target.has_value() == out_cw.has_value(),
+              "out_target and out_cw go together");
+  at::Tensor target, cw;
+  if (out_target.has_value()) {
+    // caller's buffers: int32 [nv] and weight dtype [nv], contiguous
+    CHECK_DEV(*out_target); CHECK_CONT(*out_target);
+    CHECK_DEV(*out_cw); CHECK_CONT(*out_cw);
+    TORCH_CHECK(out_target->scalar_type() == at::kInt &&
+                out_target->numel() == nv &&
+                out_cw->scalar_type() == weights.scalar_type() &&
+                out_cw->numel() == nv,
+                "out_target must be int32 [nv], out_cw weight dtype [nv]");
+    target = *out_target;
+    cw = *out_cw;
+    target.copy_(curr_comm.narrow(0, 0, nv));
+    cw.zero_();
+  } else {
+    target = curr_comm.narrow(0, 0, nv).clone();
+    cw = at::zeros({nv}, weights.options());
+  }
   auto stream = at::hip::getCurrentHIPStream().stream();
 
   const bool fork = class_streams && (vlists[4].numel() ||
@@ -216,28 +255,50 @@ std::vector<at::Tensor> local_move(
                              comm_size, comm_degree, comm_gid, constant,
                              target, cw, gid_base, n_local, next_size,
                              next_degree);
+    const int32_t* mbp = mover_bound;
+    const int32_t* cbp = cand_bound;
     auto block_class = [&](int c) {
       if (!vlists[c].numel()) return;
       const int32_t* vl = vlists[c].data_ptr<int32_t>();
       const int n = (int)vlists[c].numel();
+      hipStream_t st = block_stream;
+      if (refine) {
+        if (c == 4)
+          cuvite::launch_refine_block<W, 2048>(vl, n, args, mbp, cbp, st);
+        if (c == 5)
+          cuvite::launch_refine_block<W, 4096>(vl, n, args, mbp, cbp, st);
+        if (c == 6)
+          cuvite::launch_refine_block<W, 8192>(vl, n, args, mbp, cbp, st);
+        return;
+      }
       if (c == 4) cuvite::launch_block<W, 2048>(vl, n, args, block_stream);
       if (c == 5) cuvite::launch_block<W, 4096>(vl, n, args, block_stream);
       if (c == 6) cuvite::launch_block<W, 8192>(vl, n, args, block_stream);
     };
+    auto sub_class = [&](int c) {
+      if (!vlists[c].numel()) return;
+      const int32_t* vl = vlists[c].data_ptr<int32_t>();
+      const int n = (int)vlists[c].numel();
+      if (refine) {
+        hipStream_t st = stream;
+        if (c == 0)
+          cuvite::launch_refine_sub<W, 16, 32>(vl, n, args, mbp, cbp, st);
+        if (c == 1)
+          cuvite::launch_refine_sub<W, 64, 128>(vl, n, args, mbp, cbp, st);
+        if (c == 2)
+          cuvite::launch_refine_sub<W, 64, 512>(vl, n, args, mbp, cbp, st);
+        if (c == 3)
+          cuvite::launch_refine_sub<W, 64, 1024>(vl, n, args, mbp, cbp, st);
+        return;
+      }
+      if (c == 0) cuvite::launch_sub<W, 16, 32>(vl, n, args, stream);
+      if (c == 1) cuvite::launch_sub<W, 64, 128>(vl, n, args, stream);
+      if (c == 2) cuvite::launch_sub<W, 64, 512>(vl, n, args, stream);
+      if (c == 3) cuvite::launch_sub<W, 64, 1024>(vl, n, args, stream);
+    };
     if (fork)
       for (int c : {6, 5, 4}) block_class(c);
-    if (vlists[0].numel())
-      cuvite::launch_sub<W, 16, 32>(vlists[0].data_ptr<int32_t>(),
-                                    (int)vlists[0].numel(), args, stream);
-    if (vlists[1].numel())
-      cuvite::launch_sub<W, 64, 128>(vlists[1].data_ptr<int32_t>(),
-                                     (int)vlists[1].numel(), args, stream);
-    if (vlists[2].numel())
-      cuvite::launch_sub<W, 64, 512>(vlists[2].data_ptr<int32_t>(),
-                                     (int)vlists[2].numel(), args, stream);
-    if (vlists[3].numel())
-      cuvite::launch_sub<W, 64, 1024>(vlists[3].data_ptr<int32_t>(),
-                                      (int)vlists[3].numel(), args, stream);
+    for (int c : {0, 1, 2, 3}) sub_class(c);
     if (!fork)
       for (int c : {4, 5, 6}) block_class(c);
   });
@@ -247,6 +308,57 @@ std::vector<at::Tensor> local_move(
   }
   C10_HIP_CHECK(hipGetLastError());
   return {target, cw};
+}
+
+std::vector<at::Tensor> local_move(
+    at::Tensor rowptr, at::Tensor tails, at::Tensor weights,
+    at::Tensor curr_comm, at::Tensor v_degree, at::Tensor comm_size,
+    at::Tensor comm_degree, at::Tensor comm_gid, double constant,
+    std::vector<at::Tensor> vlists, int64_t gid_base, int64_t n_local,
+    c10::optional<at::Tensor> next_size,
+    c10::optional<at::Tensor> next_degree, bool class_streams) {
+  return local_move_impl(rowptr, tails, weights, curr_comm, v_degree,
+                         comm_size, comm_degree, comm_gid, constant, vlists,
+                         gid_base, n_local, next_size, next_degree,
+                         class_streams, nullptr, nullptr);
+}
+
+// The two bound arrays of a refine round: mover_bound int32 [>= nv] (bound
+// id of a vertex that moves this round, else -1), cand_bound int32 [nc]
+// (bound id of a dense community that may be joined this round, else -1).
+void check_bounds(const at::Tensor& mover_bound, const at::Tensor& cand_bound,
+                  int64_t nv, const at::Tensor& comm_degree) {
+  CHECK_DEV(mover_bound); CHECK_CONT(mover_bound);
+  CHECK_DEV(cand_bound); CHECK_CONT(cand_bound);
+  TORCH_CHECK(mover_bound.scalar_type() == at::kInt &&
+              cand_bound.scalar_type() == at::kInt,
+              "mover_bound / cand_bound must be int32");
+  TORCH_CHECK(mover_bound.numel() >= nv,
+              "mover_bound must cover all local vertices");
+  TORCH_CHECK(cand_bound.numel() == comm_degree.numel(),
+              "cand_bound must have one entry per dense community");
+}
+
+// One Leiden refine round over the LDS classes: local_move's kernels and
+// schedule with the candidate filter cand_bound[y] == mover_bound[v] in the
+// argmax fold, no singleton guard and no aggregate accounting. A vertex
+// with mover_bound[v] < 0 keeps its label (cw 0). out_target / out_cw:
+// optional caller-owned result buffers (both or neither).
+std::vector<at::Tensor> refine_move(
+    at::Tensor rowptr, at::Tensor tails, at::Tensor weights,
+    at::Tensor curr_comm, at::Tensor v_degree, at::Tensor comm_degree,
+    at::Tensor comm_gid, double constant, std::vector<at::Tensor> vlists,
+    at::Tensor mover_bound, at::Tensor cand_bound, int64_t gid_base,
+    int64_t n_local, bool class_streams,
+    c10::optional<at::Tensor> out_target, c10::optional<at::Tensor> out_cw) {
+  check_bounds(mover_bound, cand_bound, rowptr.numel() - 1, comm_degree);
+  // comm_size is not read by the refine kernels; comm_gid stands in for the
+  // argument (same dtype)
+  return local_move_impl(rowptr, tails, weights, curr_comm, v_degree,
+                         comm_gid, comm_degree, comm_gid, constant, vlists,
+                         gid_base, n_local, c10::nullopt, c10::nullopt,
+                         class_streams, mover_bound.data_ptr<int32_t>(),
+                         cand_bound.data_ptr<int32_t>(), out_target, out_cw);
 }
 
 at::Tensor modularity_parts(at::Tensor cluster_weight, at::Tensor comm_degree) {
@@ -320,13 +432,17 @@ std::vector<at::Tensor> csr_from_edges(int64_t nv, int64_t base,
 // eoffs: int64 [nhub + 1] segment offsets into tails_flat / weights_flat.
 // Returns per-hub (target, wcc); with next_size / next_degree the hubs are
 // also accounted in that aggregate pair.
-std::vector<at::Tensor> hub_moves(
+// With mover_bound / cand_bound the refine argmax kernels run
+// (hub_refine_moves).
+std::vector<at::Tensor> hub_moves_impl(
     at::Tensor tails_flat, at::Tensor weights_flat, at::Tensor eoffs,
     at::Tensor hubs_i32, at::Tensor hub_self, at::Tensor curr_comm,
     at::Tensor v_degree, at::Tensor comm_size, at::Tensor comm_degree,
     at::Tensor comm_gid, double constant, int64_t gid_base, int64_t n_local,
     c10::optional<at::Tensor> next_size,
-    c10::optional<at::Tensor> next_degree) {
+    c10::optional<at::Tensor> next_degree, const int32_t* mover_bound,
+    const int32_t* cand_bound) {
+  const bool refine = mover_bound != nullptr;
   CHECK_DEV(tails_flat); CHECK_CONT(tails_flat);
   CHECK_DEV(weights_flat); CHECK_CONT(weights_flat);
   CHECK_DEV(eoffs); CHECK_CONT(eoffs);
@@ -382,6 +498,20 @@ std::vector<at::Tensor> hub_moves(
     auto p_dense = at::empty({nslice}, tails_flat.options());
     auto r_key = at::empty({2 * nslice}, tails_flat.options());
     auto r_sum = at::empty({2 * nslice}, f64);
+    if (refine) {
+      cuvite::launch_hub_refine_argmax<W>(
+          keys2.data_ptr<int32_t>(), vals2.data_ptr<W>(),
+          eoffs.data_ptr<int64_t>(), hubs_i32.data_ptr<int32_t>(), nhub,
+          hub_self.data_ptr<double>(), curr_comm.data_ptr<int32_t>(),
+          v_degree.data_ptr<W>(), comm_degree.data_ptr<W>(),
+          comm_gid.data_ptr<int64_t>(), gid_base, (int32_t)n_local, constant,
+          p_wcc.data_ptr<double>(), p_gain.data_ptr<double>(),
+          p_gid.data_ptr<int64_t>(), p_dense.data_ptr<int32_t>(),
+          r_key.data_ptr<int32_t>(), r_sum.data_ptr<double>(),
+          target_hub.data_ptr<int32_t>(), cw_hub.data_ptr<W>(), mover_bound,
+          cand_bound, stream);
+      return;
+    }
     cuvite::launch_hub_argmax<W>(
         keys2.data_ptr<int32_t>(), vals2.data_ptr<W>(),
         eoffs.data_ptr<int64_t>(), hubs_i32.data_ptr<int32_t>(), nhub,
@@ -399,6 +529,35 @@ std::vector<at::Tensor> hub_moves(
   });
   C10_HIP_CHECK(hipGetLastError());
   return {target_hub, cw_hub};
+}
+
+std::vector<at::Tensor> hub_moves(
+    at::Tensor tails_flat, at::Tensor weights_flat, at::Tensor eoffs,
+    at::Tensor hubs_i32, at::Tensor hub_self, at::Tensor curr_comm,
+    at::Tensor v_degree, at::Tensor comm_size, at::Tensor comm_degree,
+    at::Tensor comm_gid, double constant, int64_t gid_base, int64_t n_local,
+    c10::optional<at::Tensor> next_size,
+    c10::optional<at::Tensor> next_degree) {
+  return hub_moves_impl(tails_flat, weights_flat, eoffs, hubs_i32, hub_self,
+                        curr_comm, v_degree, comm_size, comm_degree, comm_gid,
+                        constant, gid_base, n_local, next_size, next_degree,
+                        nullptr, nullptr);
+}
+
+// One refine round for hub vertices: hub_moves with the refine argmax
+// kernels. mover_bound is indexed by the dense vertex id (hubs_i32 entries).
+std::vector<at::Tensor> hub_refine_moves(
+    at::Tensor tails_flat, at::Tensor weights_flat, at::Tensor eoffs,
+    at::Tensor hubs_i32, at::Tensor hub_self, at::Tensor curr_comm,
+    at::Tensor v_degree, at::Tensor comm_degree, at::Tensor comm_gid,
+    double constant, at::Tensor mover_bound, at::Tensor cand_bound,
+    int64_t gid_base, int64_t n_local) {
+  check_bounds(mover_bound, cand_bound, v_degree.numel(), comm_degree);
+  return hub_moves_impl(tails_flat, weights_flat, eoffs, hubs_i32, hub_self,
+                        curr_comm, v_degree, comm_gid, comm_degree, comm_gid,
+                        constant, gid_base, n_local, c10::nullopt,
+                        c10::nullopt, mover_bound.data_ptr<int32_t>(),
+                        cand_bound.data_ptr<int32_t>());
 }
 
 // Fresh world-1 recount of the community aggregates (see recount_kernel).
@@ -638,6 +797,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("vlists"), py::arg("gid_base") = 0, py::arg("n_local") = 0,
         py::arg("next_size") = py::none(),
         py::arg("next_degree") = py::none(), py::arg("class_streams") = true);
+  m.def("refine_move_bucketed", &refine_move,
+        "Leiden refine round (HIP, degree-class routed, bound-filtered)",
+        py::arg("rowptr"), py::arg("tails"), py::arg("weights"),
+        py::arg("curr_comm"), py::arg("v_degree"), py::arg("comm_degree"),
+        py::arg("comm_gid"), py::arg("constant"), py::arg("vlists"),
+        py::arg("mover_bound"), py::arg("cand_bound"),
+        py::arg("gid_base") = 0, py::arg("n_local") = 0,
+        py::arg("class_streams") = true,
+        py::arg("out_target") = py::none(), py::arg("out_cw") = py::none());
+  m.def("hub_refine_moves", &hub_refine_moves,
+        "Leiden refine round for hub vertices: segsort + bound-filtered "
+        "sliced argmax",
+        py::arg("tails_flat"), py::arg("weights_flat"), py::arg("eoffs"),
+        py::arg("hubs_i32"), py::arg("hub_self"), py::arg("curr_comm"),
+        py::arg("v_degree"), py::arg("comm_degree"), py::arg("comm_gid"),
+        py::arg("constant"), py::arg("mover_bound"), py::arg("cand_bound"),
+        py::arg("gid_base") = 0, py::arg("n_local") = 0);
   m.def("modularity_parts", &modularity_parts,
         "fp64 (sum cw, sum degree^2) reduction (HIP)");
   m.def("scatter_add_", &scatter_add_,

@@ -59,6 +59,16 @@
 // (gid_of); with a second aggregate pair the lanes that store a target also
 // account the new community sizes and degrees (account_target), which
 // replaces the recount pass after a single-rank sweep.
+//
+// The move kernels (lv_move_sub, lv_move_block, hub_slice_kernel,
+// hub_final_kernel) take a `bool REFINE` template parameter. false is the
+// local move described above; its instantiations compile to the instructions
+// they had before the parameter existed. true is one round of the Leiden
+// refinement (cuvite_amd/refine.py): only the vertices with mover_bound[v] >=
+// 0 move, a candidate y counts only if cand_bound[y] == mover_bound[v]
+// (checked where its gain is folded into the argmax, one 4-byte gather per
+// distinct candidate), and there is neither singleton guard nor aggregate
+// accounting.
 
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
@@ -211,17 +221,23 @@ DEV_INLINE double insert_edges_pipelined(
   return selfloop;
 }
 
-// Scan the table slots owned by this lane and fold the argmax.
-template <typename W>
+// Scan the table slots owned by this lane and fold the argmax. REFINE: a
+// candidate counts only if cand_bound[y] equals the mover's bound `mb` (one
+// 4-byte gather per distinct candidate, here and not at insert, which would
+// pay it per edge).
+template <typename W, bool REFINE>
 DEV_INLINE void scan_slots(const int32_t* keys, const W* vals, int cap,
                            int lane, int lanes, int32_t cc, double eix,
                            double ax, double vdeg, double constant,
                            const W* __restrict__ comm_degree,
                            const int64_t* __restrict__ comm_gid,
-                           int64_t gid_base, int32_t n_local, Best& best) {
+                           int64_t gid_base, int32_t n_local, Best& best,
+                           int32_t mb,
+                           const int32_t* __restrict__ cand_bound) {
   for (int s = lane; s < cap; s += lanes) {
     int32_t y = keys[s];
     if (y == EMPTY_KEY || y == cc) continue;
+    if (REFINE && cand_bound[y] != mb) continue;
     double eiy = (double)vals[s];
     double ay = (double)comm_degree[y];
     double g = 2.0 * (eiy - eix) - 2.0 * vdeg * (ay - ax) * constant;
@@ -245,7 +261,14 @@ DEV_INLINE int cap_for_degree(int64_t deg, int CAP, int lo) {
   return cap;
 }
 
-template <typename W, int LANES, int CAP, int BLOCK>
+// REFINE = false is the plain local move (mover_bound and cand_bound are not
+// read; the launcher passes null). REFINE = true is one Leiden refinement
+// round (see local_move.refine_move_torch): a vertex with mover_bound[v] < 0
+// does not move this round and is treated like the -1 padding, so it still
+// reaches both barriers beside the movers of its block and keeps target = own
+// label; candidates are filtered by their bound in scan_slots; no singleton
+// guard and no fused aggregate accounting (comm_size, next_* are not read).
+template <typename W, int LANES, int CAP, int BLOCK, bool REFINE>
 __global__ __launch_bounds__(BLOCK) void lv_move_sub(
     const int32_t* __restrict__ vlist, int nlist,
     const int64_t* __restrict__ rowptr, const int32_t* __restrict__ tails,
@@ -255,7 +278,8 @@ __global__ __launch_bounds__(BLOCK) void lv_move_sub(
     double constant, int32_t* __restrict__ target,
     W* __restrict__ cluster_weight, int64_t gid_base, int32_t n_local,
     int64_t* __restrict__ next_size, W* __restrict__ next_degree,
-    int64_t n_next) {
+    int64_t n_next, const int32_t* __restrict__ mover_bound,
+    const int32_t* __restrict__ cand_bound) {
   constexpr int GROUPS = BLOCK / LANES;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   W* vals = (W*)smem;
@@ -264,7 +288,12 @@ __global__ __launch_bounds__(BLOCK) void lv_move_sub(
   const int group = threadIdx.x / LANES;
   const int lane = threadIdx.x % LANES;
   const int gidx = blockIdx.x * GROUPS + group;
-  const int32_t v = (gidx < nlist) ? vlist[gidx] : -1;
+  int32_t v = (gidx < nlist) ? vlist[gidx] : -1;
+  int32_t mb = -1;
+  if (REFINE && v >= 0) {
+    mb = mover_bound[v];
+    if (mb < 0) v = -1;
+  }
 
   int32_t* gkeys = keys + (size_t)group * CAP;
   W* gvals = vals + (size_t)group * CAP;
@@ -298,17 +327,20 @@ __global__ __launch_bounds__(BLOCK) void lv_move_sub(
     double ax = (double)comm_degree[cc] - vdeg;
     const int64_t gid_cc = gid_of(comm_gid, gid_base, n_local, cc);
     best.gid = gid_cc;
-    scan_slots(gkeys, gvals, cap, lane, LANES, cc, eix, ax, vdeg, constant,
-               comm_degree, comm_gid, gid_base, n_local, best);
+    scan_slots<W, REFINE>(gkeys, gvals, cap, lane, LANES, cc, eix, ax, vdeg,
+                          constant, comm_degree, comm_gid, gid_base, n_local,
+                          best, mb, cand_bound);
     best_reduce<LANES>(best);
     if (lane == 0) {
       int32_t tgt = best.dense;
       // singleton-swap guard (louvain.cpp:2238-2239)
-      if (comm_size[tgt] == 1 && comm_size[cc] == 1 && best.gid > gid_cc)
+      if (!REFINE && comm_size[tgt] == 1 && comm_size[cc] == 1 &&
+          best.gid > gid_cc)
         tgt = cc;
       target[v] = tgt;
       cluster_weight[v] = wcc;
-      account_target(next_size, next_degree, n_next, tgt, vdeg_w);
+      if (!REFINE)
+        account_target(next_size, next_degree, n_next, tgt, vdeg_w);
     }
   }
 }
@@ -317,7 +349,10 @@ __global__ __launch_bounds__(BLOCK) void lv_move_sub(
 // Block kernel: one 256-thread block per vertex, CAP-slot LDS table.
 // ---------------------------------------------------------------------------
 
-template <typename W, int CAP, int BLOCK>
+// REFINE as in lv_move_sub; the whole block serves one vertex, so a
+// non-mover leaves before any barrier (block-uniform) and keeps target = own
+// label.
+template <typename W, int CAP, int BLOCK, bool REFINE>
 __global__ __launch_bounds__(BLOCK) void lv_move_block(
     const int32_t* __restrict__ vlist, int nlist,
     const int64_t* __restrict__ rowptr, const int32_t* __restrict__ tails,
@@ -327,7 +362,8 @@ __global__ __launch_bounds__(BLOCK) void lv_move_block(
     double constant, int32_t* __restrict__ target,
     W* __restrict__ cluster_weight, int64_t gid_base, int32_t n_local,
     int64_t* __restrict__ next_size, W* __restrict__ next_degree,
-    int64_t n_next) {
+    int64_t n_next, const int32_t* __restrict__ mover_bound,
+    const int32_t* __restrict__ cand_bound) {
   constexpr int WAVES = BLOCK / 64;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   W* vals = (W*)smem;
@@ -338,6 +374,11 @@ __global__ __launch_bounds__(BLOCK) void lv_move_block(
   __shared__ double red_self[WAVES];
 
   const int32_t v = vlist[blockIdx.x];
+  int32_t mb = -1;
+  if (REFINE) {
+    mb = mover_bound[v];
+    if (mb < 0) return;
+  }
   const int tid = threadIdx.x;
   const int wave = tid / 64, lane = tid % 64;
 
@@ -367,8 +408,9 @@ __global__ __launch_bounds__(BLOCK) void lv_move_block(
   double ax = (double)comm_degree[cc] - vdeg;
   const int64_t gid_cc = gid_of(comm_gid, gid_base, n_local, cc);
   Best best{0.0, gid_cc, cc};
-  scan_slots(keys, vals, cap, tid, BLOCK, cc, eix, ax, vdeg, constant,
-             comm_degree, comm_gid, gid_base, n_local, best);
+  scan_slots<W, REFINE>(keys, vals, cap, tid, BLOCK, cc, eix, ax, vdeg,
+                        constant, comm_degree, comm_gid, gid_base, n_local,
+                        best, mb, cand_bound);
   best_reduce<64>(best);
   if (lane == 0) {
     red_gain[wave] = best.gain;
@@ -381,11 +423,12 @@ __global__ __launch_bounds__(BLOCK) void lv_move_block(
     for (int i = 1; i < WAVES; i++)
       best_combine(best, red_gain[i], red_gid[i], red_dense[i]);
     int32_t tgt = best.dense;
-    if (comm_size[tgt] == 1 && comm_size[cc] == 1 && best.gid > gid_cc)
+    if (!REFINE && comm_size[tgt] == 1 && comm_size[cc] == 1 &&
+        best.gid > gid_cc)
       tgt = cc;
     target[v] = tgt;
     cluster_weight[v] = wcc;
-    account_target(next_size, next_degree, n_next, tgt, vdeg_w);
+    if (!REFINE) account_target(next_size, next_degree, n_next, tgt, vdeg_w);
   }
 }
 
@@ -978,7 +1021,11 @@ __global__ __launch_bounds__(BLOCK) void hub_own_weight_kernel(
   if (lane == 0) p_wcc[w] = acc;
 }
 
-template <typename W, int BLOCK>
+// REFINE (a refinement round, as in lv_move_sub): a hub that does not move
+// this round leaves at once (wave-uniform; hub_final_kernel does not read
+// its slice records), and a run's gain is folded only if the run's community
+// has the mover's bound.
+template <typename W, int BLOCK, bool REFINE>
 __global__ __launch_bounds__(BLOCK) void hub_slice_kernel(
     const int32_t* __restrict__ keys, const W* __restrict__ vals,
     const int64_t* __restrict__ eoffs, const int32_t* __restrict__ hubs,
@@ -988,7 +1035,8 @@ __global__ __launch_bounds__(BLOCK) void hub_slice_kernel(
     const int64_t* __restrict__ comm_gid, int64_t gid_base, int32_t n_local,
     double constant, double* __restrict__ p_gain, int64_t* __restrict__ p_gid,
     int32_t* __restrict__ p_dense, int32_t* __restrict__ r_key,
-    double* __restrict__ r_sum) {
+    double* __restrict__ r_sum, const int32_t* __restrict__ mover_bound,
+    const int32_t* __restrict__ cand_bound) {
   constexpr int WAVES = BLOCK / 64;
   const int lane = threadIdx.x % 64;
   const int64_t w = (int64_t)blockIdx.x * WAVES + threadIdx.x / 64;
@@ -996,6 +1044,11 @@ __global__ __launch_bounds__(BLOCK) void hub_slice_kernel(
   const int part = (int)(w % HUB_SLICES);
   if (hidx >= nhub) return;
   const int32_t v = hubs[hidx];
+  int32_t mb = -1;
+  if (REFINE) {
+    mb = mover_bound[v];
+    if (mb < 0) return;
+  }
   const int32_t cc = curr_comm[v];
   const int64_t b = eoffs[hidx], e = eoffs[hidx + 1];
   const int64_t len = e - b;
@@ -1052,7 +1105,7 @@ __global__ __launch_bounds__(BLOCK) void hub_slice_kernel(
         } else if (kk == last_key) {
           r_key[2 * w + 1] = kk;
           r_sum[2 * w + 1] = val;
-        } else if (kk != cc) {
+        } else if (kk != cc && (!REFINE || cand_bound[kk] == mb)) {
           const double eiy = (double)(W)val;
           const double ay = (double)comm_degree[kk];
           const double g =
@@ -1074,7 +1127,11 @@ __global__ __launch_bounds__(BLOCK) void hub_slice_kernel(
   }
 }
 
-template <typename W, int BLOCK>
+// REFINE: a hub that does not move this round keeps its label (cw 0, like a
+// vertex the class kernels skip); the stitched runs pass the same bound
+// filter as the runs inside a slice; no singleton guard, no aggregate
+// accounting.
+template <typename W, int BLOCK, bool REFINE>
 __global__ __launch_bounds__(BLOCK) void hub_final_kernel(
     const int32_t* __restrict__ hubs, int nhub,
     const double* __restrict__ hub_self, const double* __restrict__ p_wcc,
@@ -1086,13 +1143,25 @@ __global__ __launch_bounds__(BLOCK) void hub_final_kernel(
     const int32_t* __restrict__ r_key, const double* __restrict__ r_sum,
     int32_t* __restrict__ target_hub, W* __restrict__ cw_hub,
     int64_t* __restrict__ next_size, W* __restrict__ next_degree,
-    int64_t n_next) {
+    int64_t n_next, const int32_t* __restrict__ mover_bound,
+    const int32_t* __restrict__ cand_bound) {
   constexpr int WAVES = BLOCK / 64;
   const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
   const int hidx = blockIdx.x * WAVES + wave;
   if (hidx >= nhub) return;
   const int32_t v = hubs[hidx];
   const int32_t cc = curr_comm[v];
+  int32_t mb = -1;
+  if (REFINE) {
+    mb = mover_bound[v];
+    if (mb < 0) {  // wave-uniform
+      if (lane == 0) {
+        target_hub[hidx] = cc;
+        cw_hub[hidx] = (W)0;
+      }
+      return;
+    }
+  }
   const W wcc = (W)hub_own_weight(p_wcc, hidx, lane);
   const double eix = (double)wcc - hub_self[hidx];
   const W vdeg_w = v_degree[v];
@@ -1119,7 +1188,7 @@ __global__ __launch_bounds__(BLOCK) void hub_final_kernel(
       if (j < lane) leader = false;
     }
   }
-  if (leader && key != cc) {
+  if (leader && key != cc && (!REFINE || cand_bound[key] == mb)) {
     const double eiy = (double)(W)total;
     const double ay = (double)comm_degree[key];
     const double g = 2.0 * (eiy - eix) - 2.0 * vdeg * (ay - ax) * constant;
@@ -1129,11 +1198,12 @@ __global__ __launch_bounds__(BLOCK) void hub_final_kernel(
   if (lane == 0) {
     int32_t tgt = best.dense;
     // singleton-swap guard (louvain.cpp:2238-2239)
-    if (comm_size[tgt] == 1 && comm_size[cc] == 1 && best.gid > gid_cc)
+    if (!REFINE && comm_size[tgt] == 1 && comm_size[cc] == 1 &&
+        best.gid > gid_cc)
       tgt = cc;
     target_hub[hidx] = tgt;
     cw_hub[hidx] = wcc;
-    account_target(next_size, next_degree, n_next, tgt, vdeg_w);
+    if (!REFINE) account_target(next_size, next_degree, n_next, tgt, vdeg_w);
   }
 }
 
@@ -1166,14 +1236,17 @@ struct MoveArgs {
   int64_t n_next;       // length of next_size / next_degree
 };
 
-template <typename W, int LANES, int CAP>
-void launch_sub(const int32_t* vlist, int nlist, const MoveArgs<W>& a,
-                hipStream_t stream) {
+// REFINE = false: the plain kernels (the bound arrays are null and not
+// read); REFINE = true: the refine kernels, same grids and tables.
+template <typename W, int LANES, int CAP, bool REFINE>
+static void launch_sub_impl(const int32_t* vlist, int nlist,
+                            const MoveArgs<W>& a, const int32_t* mover_bound,
+                            const int32_t* cand_bound, hipStream_t stream) {
   constexpr int BLOCK = 256;
   constexpr int GROUPS = BLOCK / LANES;
   const int grid = (nlist + GROUPS - 1) / GROUPS;
   const size_t shmem = (size_t)GROUPS * CAP * (sizeof(W) + sizeof(int32_t));
-  auto kern = lv_move_sub<W, LANES, CAP, BLOCK>;
+  auto kern = lv_move_sub<W, LANES, CAP, BLOCK, REFINE>;
   if (shmem > 65536)
     (void)hipFuncSetAttribute((const void*)kern,
                               hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1182,15 +1255,18 @@ void launch_sub(const int32_t* vlist, int nlist, const MoveArgs<W>& a,
                      nlist, a.rowptr, a.tails, a.weights, a.curr_comm,
                      a.v_degree, a.comm_size, a.comm_degree, a.comm_gid,
                      a.constant, a.target, a.cluster_weight, a.gid_base,
-                     a.n_local, a.next_size, a.next_degree, a.n_next);
+                     a.n_local, a.next_size, a.next_degree, a.n_next,
+                     mover_bound, cand_bound);
 }
 
-template <typename W, int CAP>
-void launch_block(const int32_t* vlist, int nlist, const MoveArgs<W>& a,
-                  hipStream_t stream) {
+template <typename W, int CAP, bool REFINE>
+static void launch_block_impl(const int32_t* vlist, int nlist,
+                              const MoveArgs<W>& a,
+                              const int32_t* mover_bound,
+                              const int32_t* cand_bound, hipStream_t stream) {
   constexpr int BLOCK = 256;
   const size_t shmem = (size_t)CAP * (sizeof(W) + sizeof(int32_t));
-  auto kern = lv_move_block<W, CAP, BLOCK>;
+  auto kern = lv_move_block<W, CAP, BLOCK, REFINE>;
   if (shmem > 65536)
     (void)hipFuncSetAttribute((const void*)kern,
                               hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1199,8 +1275,65 @@ void launch_block(const int32_t* vlist, int nlist, const MoveArgs<W>& a,
                      nlist, a.rowptr, a.tails, a.weights, a.curr_comm,
                      a.v_degree, a.comm_size, a.comm_degree, a.comm_gid,
                      a.constant, a.target, a.cluster_weight, a.gid_base,
-                     a.n_local, a.next_size, a.next_degree, a.n_next);
+                     a.n_local, a.next_size, a.next_degree, a.n_next,
+                     mover_bound, cand_bound);
 }
+
+template <typename W, int LANES, int CAP>
+void launch_sub(const int32_t* vlist, int nlist, const MoveArgs<W>& a,
+                hipStream_t stream) {
+  launch_sub_impl<W, LANES, CAP, false>(vlist, nlist, a, nullptr, nullptr,
+                                        stream);
+}
+
+template <typename W, int CAP>
+void launch_block(const int32_t* vlist, int nlist, const MoveArgs<W>& a,
+                  hipStream_t stream) {
+  launch_block_impl<W, CAP, false>(vlist, nlist, a, nullptr, nullptr, stream);
+}
+
+// Refine round: a.comm_size and the next_* pair are not read.
+template <typename W, int LANES, int CAP>
+void launch_refine_sub(const int32_t* vlist, int nlist, const MoveArgs<W>& a,
+                       const int32_t* mover_bound, const int32_t* cand_bound,
+                       hipStream_t stream) {
+  launch_sub_impl<W, LANES, CAP, true>(vlist, nlist, a, mover_bound,
+                                       cand_bound, stream);
+}
+
+template <typename W, int CAP>
+void launch_refine_block(const int32_t* vlist, int nlist,
+                         const MoveArgs<W>& a, const int32_t* mover_bound,
+                         const int32_t* cand_bound, hipStream_t stream) {
+  launch_block_impl<W, CAP, true>(vlist, nlist, a, mover_bound, cand_bound,
+                                  stream);
+}
+
+#define INSTANTIATE_REFINE(W)                                                 \
+  template void launch_refine_sub<W, 16, 32>(                                 \
+      const int32_t*, int, const MoveArgs<W>&, const int32_t*,                \
+      const int32_t*, hipStream_t);                                           \
+  template void launch_refine_sub<W, 64, 128>(                                \
+      const int32_t*, int, const MoveArgs<W>&, const int32_t*,                \
+      const int32_t*, hipStream_t);                                           \
+  template void launch_refine_sub<W, 64, 512>(                                \
+      const int32_t*, int, const MoveArgs<W>&, const int32_t*,                \
+      const int32_t*, hipStream_t);                                           \
+  template void launch_refine_sub<W, 64, 1024>(                               \
+      const int32_t*, int, const MoveArgs<W>&, const int32_t*,                \
+      const int32_t*, hipStream_t);                                           \
+  template void launch_refine_block<W, 2048>(                                 \
+      const int32_t*, int, const MoveArgs<W>&, const int32_t*,                \
+      const int32_t*, hipStream_t);                                           \
+  template void launch_refine_block<W, 4096>(                                 \
+      const int32_t*, int, const MoveArgs<W>&, const int32_t*,                \
+      const int32_t*, hipStream_t);                                           \
+  template void launch_refine_block<W, 8192>(                                 \
+      const int32_t*, int, const MoveArgs<W>&, const int32_t*,                \
+      const int32_t*, hipStream_t);
+
+INSTANTIATE_REFINE(float)
+INSTANTIATE_REFINE(double)
 
 // explicit instantiations used by bindings.cpp
 #define INSTANTIATE(W)                                                        \
@@ -1360,16 +1493,19 @@ void launch_hub_argmax(const int32_t* keys, const W* vals,
   hipLaunchKernelGGL((hub_own_weight_kernel<W, BLOCK>), slice_grid,
                      dim3(BLOCK), 0, stream, keys, vals, eoffs, hubs, nhub,
                      curr_comm, p_wcc);
-  hipLaunchKernelGGL((hub_slice_kernel<W, BLOCK>), slice_grid, dim3(BLOCK), 0,
-                     stream, keys, vals, eoffs, hubs, nhub, hub_self, p_wcc,
-                     curr_comm, v_degree, comm_degree, comm_gid, gid_base,
-                     n_local, constant, p_gain, p_gid, p_dense, r_key, r_sum);
-  hipLaunchKernelGGL((hub_final_kernel<W, BLOCK>),
+  const int32_t* no_bound = nullptr;
+  hipLaunchKernelGGL((hub_slice_kernel<W, BLOCK, false>), slice_grid,
+                     dim3(BLOCK), 0, stream, keys, vals, eoffs, hubs, nhub,
+                     hub_self, p_wcc, curr_comm, v_degree, comm_degree,
+                     comm_gid, gid_base, n_local, constant, p_gain, p_gid,
+                     p_dense, r_key, r_sum, no_bound, no_bound);
+  hipLaunchKernelGGL((hub_final_kernel<W, BLOCK, false>),
                      dim3((nhub + WAVES - 1) / WAVES), dim3(BLOCK), 0, stream,
                      hubs, nhub, hub_self, p_wcc, curr_comm, v_degree,
                      comm_size, comm_degree, comm_gid, gid_base, n_local,
                      constant, p_gain, p_gid, p_dense, r_key, r_sum,
-                     target_hub, cw_hub, next_size, next_degree, n_next);
+                     target_hub, cw_hub, next_size, next_degree, n_next,
+                     no_bound, no_bound);
 }
 #define INSTANTIATE_HUB(W)                                                    \
   template void launch_hub_argmax<W>(                                         \
@@ -1380,6 +1516,51 @@ void launch_hub_argmax(const int32_t* keys, const W* vals,
       hipStream_t);
 INSTANTIATE_HUB(float)
 INSTANTIATE_HUB(double)
+
+// Refine variant of launch_hub_argmax: the own-weight kernel is shared, the
+// slice and final kernels are their REFINE instantiations.
+template <typename W>
+void launch_hub_refine_argmax(
+    const int32_t* keys, const W* vals, const int64_t* eoffs,
+    const int32_t* hubs, int nhub, const double* hub_self,
+    const int32_t* curr_comm, const W* v_degree, const W* comm_degree,
+    const int64_t* comm_gid, int64_t gid_base, int32_t n_local,
+    double constant, double* p_wcc, double* p_gain, int64_t* p_gid,
+    int32_t* p_dense, int32_t* r_key, double* r_sum, int32_t* target_hub,
+    W* cw_hub, const int32_t* mover_bound, const int32_t* cand_bound,
+    hipStream_t stream) {
+  if (nhub == 0) return;
+  constexpr int BLOCK = 256;
+  constexpr int WAVES = BLOCK / 64;
+  const dim3 slice_grid((uint32_t)nhub * (HUB_SLICES / WAVES));
+  hipLaunchKernelGGL((hub_own_weight_kernel<W, BLOCK>), slice_grid,
+                     dim3(BLOCK), 0, stream, keys, vals, eoffs, hubs, nhub,
+                     curr_comm, p_wcc);
+  hipLaunchKernelGGL((hub_slice_kernel<W, BLOCK, true>), slice_grid,
+                     dim3(BLOCK), 0, stream, keys, vals, eoffs, hubs, nhub,
+                     hub_self, p_wcc, curr_comm, v_degree, comm_degree,
+                     comm_gid, gid_base, n_local, constant, p_gain, p_gid,
+                     p_dense, r_key, r_sum, mover_bound, cand_bound);
+  const int64_t* no_size = nullptr;
+  int64_t* no_next_size = nullptr;
+  W* no_next_degree = nullptr;
+  hipLaunchKernelGGL((hub_final_kernel<W, BLOCK, true>),
+                     dim3((nhub + WAVES - 1) / WAVES), dim3(BLOCK), 0, stream,
+                     hubs, nhub, hub_self, p_wcc, curr_comm, v_degree,
+                     no_size, comm_degree, comm_gid, gid_base, n_local,
+                     constant, p_gain, p_gid, p_dense, r_key, r_sum,
+                     target_hub, cw_hub, no_next_size, no_next_degree,
+                     (int64_t)0, mover_bound, cand_bound);
+}
+#define INSTANTIATE_HUB_REFINE(W)                                             \
+  template void launch_hub_refine_argmax<W>(                                  \
+      const int32_t*, const W*, const int64_t*, const int32_t*, int,          \
+      const double*, const int32_t*, const W*, const W*, const int64_t*,      \
+      int64_t, int32_t, double, double*, double*, int64_t*, int32_t*,         \
+      int32_t*, double*, int32_t*, W*, const int32_t*, const int32_t*,        \
+      hipStream_t);
+INSTANTIATE_HUB_REFINE(float)
+INSTANTIATE_HUB_REFINE(double)
 
 int hub_slices() { return HUB_SLICES; }
 
