@@ -58,7 +58,7 @@ def _hub_cut() -> int:
 
 def _buckets_for(rowptr: torch.Tensor):
     """Degree-class vertex lists for a CSR (static per phase; cached by the
-    rowptr storage). Returns (vlists[5] for the LDS class kernels,
+    rowptr storage). Returns (vlists[7] for the LDS class kernels,
     hubs64 int64 hub vertex list, hdeg int64 hub degrees)."""
     cut = _hub_cut()
     key = (rowptr.data_ptr(), rowptr.numel(), cut)
@@ -361,6 +361,37 @@ def _class_streams_enabled() -> bool:
     return os.environ.get("CUVITE_CLASS_STREAMS", "1") not in ("0", "off")
 
 
+def _classes_beside_hubs(dev, hubs64, run_hub_sort, classes, hub_moves):
+    """Shared tail of local_move and refine_move. `classes()` launches the
+    degree-class kernels and returns (target [nv], cw [nv]); `hub_moves()`
+    runs the hub pipeline and returns the per-hub pair aligned with hubs64,
+    which is scattered into the class result. With `run_hub_sort` false only
+    the classes run."""
+    if run_hub_sort and not os.environ.get("CUVITE_NO_OVERLAP"):
+        # disjoint vertex sets: run the HIP class kernels on a side stream
+        # concurrently with the (longer) hub pipeline on the main stream;
+        # hub results come back as separate tensors and are scattered after
+        # the join (no cross-stream writes into the class kernels' outputs)
+        main = torch.cuda.current_stream(dev)
+        side = _side_stream(dev)
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            target, cw = classes()
+        hub_tgt, hub_cw = hub_moves()
+        main.wait_stream(side)
+        target.record_stream(main)
+        cw.record_stream(main)
+        target[hubs64] = hub_tgt
+        cw[hubs64] = hub_cw
+        return target, cw
+    target, cw = classes()
+    if run_hub_sort:
+        hub_tgt, hub_cw = hub_moves()
+        target[hubs64] = hub_tgt
+        cw[hubs64] = hub_cw
+    return target, cw
+
+
 def local_move(inp, next_size=None, next_degree=None):
     """HIP local-move iteration (see local_move.MoveInputs for semantics).
     Returns (target dense comm ids [nv], cluster_weight [nv]).
@@ -429,37 +460,16 @@ def local_move(inp, next_size=None, next_degree=None):
                   f"{time.perf_counter() - t0:.3f}s", file=sys.stderr,
                   flush=True)
         return target, cw
-    run_hub_sort = hubs64.numel() > 0
-    overlap = run_hub_sort and not os.environ.get("CUVITE_NO_OVERLAP")
-    if overlap:
-        # disjoint vertex sets: run the HIP class kernels on a side stream
-        # concurrently with the (longer) hub pipeline on the main stream;
-        # hub results come back as separate tensors and are scattered after
-        # the join (no cross-stream writes into the class kernels' outputs)
-        main = torch.cuda.current_stream(dev)
-        side = _side_stream(dev)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            target, cw = ext.local_move_bucketed(
-                inp.rowptr, inp.tails, inp.weights, inp.curr_comm,
-                inp.v_degree, inp.comm_size, inp.comm_degree, inp.comm_gid,
-                float(inp.constant), vlists, **kw)
-        hub_tgt, hub_cw = _hub_moves_sorted(inp, hubs64, hdeg, nxt)
-        main.wait_stream(side)
-        target.record_stream(main)
-        cw.record_stream(main)
-        target[hubs64] = hub_tgt
-        cw[hubs64] = hub_cw
-        return target, cw
-    target, cw = ext.local_move_bucketed(
-        inp.rowptr, inp.tails, inp.weights, inp.curr_comm, inp.v_degree,
-        inp.comm_size, inp.comm_degree, inp.comm_gid, float(inp.constant),
-        vlists, **kw)
-    if run_hub_sort:
-        hub_tgt, hub_cw = _hub_moves_sorted(inp, hubs64, hdeg, nxt)
-        target[hubs64] = hub_tgt
-        cw[hubs64] = hub_cw
-    return target, cw
+
+    def classes():
+        return ext.local_move_bucketed(
+            inp.rowptr, inp.tails, inp.weights, inp.curr_comm, inp.v_degree,
+            inp.comm_size, inp.comm_degree, inp.comm_gid, float(inp.constant),
+            vlists, **kw)
+
+    return _classes_beside_hubs(
+        dev, hubs64, hubs64.numel() > 0, classes,
+        lambda: _hub_moves_sorted(inp, hubs64, hdeg, nxt))
 
 
 def refine_move(inp, mover_bound: torch.Tensor, cand_bound: torch.Tensor,
@@ -494,27 +504,9 @@ def refine_move(inp, mover_bound: torch.Tensor, cand_bound: torch.Tensor,
             out_cw=None if out is None else out[1])
 
     bounds = (mover_bound, cand_bound)
-    if run_hub_sort and not os.environ.get("CUVITE_NO_OVERLAP"):
-        # as in local_move: class kernels on the side stream beside the hub
-        # pipeline, hub results scattered after the join
-        main = torch.cuda.current_stream(dev)
-        side = _side_stream(dev)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            target, cw = classes()
-        hub_tgt, hub_cw = _hub_moves_sorted(inp, hubs64, hdeg, None, bounds)
-        main.wait_stream(side)
-        target.record_stream(main)
-        cw.record_stream(main)
-        target[hubs64] = hub_tgt
-        cw[hubs64] = hub_cw
-        return target, cw
-    target, cw = classes()
-    if run_hub_sort:
-        hub_tgt, hub_cw = _hub_moves_sorted(inp, hubs64, hdeg, None, bounds)
-        target[hubs64] = hub_tgt
-        cw[hubs64] = hub_cw
-    return target, cw
+    return _classes_beside_hubs(
+        dev, hubs64, run_hub_sort, classes,
+        lambda: _hub_moves_sorted(inp, hubs64, hdeg, None, bounds))
 
 
 def modularity_parts(cluster_weight: torch.Tensor,

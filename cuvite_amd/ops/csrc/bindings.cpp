@@ -4,106 +4,31 @@
 #include <hip/hip_runtime.h>
 #include <c10/hip/HIPStream.h>
 
+#include "launch.h"
+
 #include <cstdint>
 #include <tuple>
 #include <vector>
 
-namespace cuvite {
-
-template <typename W>
-struct MoveArgs {
-  const int64_t* rowptr;
-  const int32_t* tails;
-  const W* weights;
-  const int32_t* curr_comm;
-  const W* v_degree;
-  const int64_t* comm_size;
-  const W* comm_degree;
-  const int64_t* comm_gid;
-  double constant;
-  int32_t* target;
-  W* cluster_weight;
-  int64_t gid_base;
-  int32_t n_local;
-  int64_t* next_size;
-  W* next_degree;
-  int64_t n_next;
-};
-
-template <typename W, int LANES, int CAP>
-void launch_sub(const int32_t*, int, const MoveArgs<W>&, hipStream_t);
-template <typename W, int CAP>
-void launch_block(const int32_t*, int, const MoveArgs<W>&, hipStream_t);
-template <typename W, int LANES, int CAP>
-void launch_refine_sub(const int32_t*, int, const MoveArgs<W>&,
-                       const int32_t*, const int32_t*, hipStream_t);
-template <typename W, int CAP>
-void launch_refine_block(const int32_t*, int, const MoveArgs<W>&,
-                         const int32_t*, const int32_t*, hipStream_t);
-template <typename W>
-void launch_modularity(const W*, const W*, int64_t, double*, hipStream_t);
-template <typename W>
-void launch_scatter_add(W*, const int64_t*, const W*, int64_t, hipStream_t);
-void launch_degree_count(const int64_t*, int64_t, int64_t, int32_t*,
-                         hipStream_t);
-template <typename W>
-void launch_csr_place(const int64_t*, const int64_t*, const W*, int64_t,
-                      int64_t, const int64_t*, int32_t*, int64_t*, W*,
-                      hipStream_t);
-template <typename W>
-void launch_row_sum(const int64_t*, const W*, int64_t, W*, hipStream_t);
-void launch_gather_comm(const int32_t*, const int32_t*, int64_t, int32_t*,
-                        hipStream_t);
-template <typename W>
-void segsort_pairs(void*, size_t*, const int32_t*, int32_t*, const W*, W*,
-                   int64_t, int, const int64_t*, int, hipStream_t);
-template <typename W>
-void reduce_by_key64(void*, size_t*, const int64_t*, const W*, int64_t,
-                     int64_t*, W*, unsigned int*, hipStream_t);
-template <typename W>
-void sort_pairs64(void*, size_t*, const int64_t*, int64_t*, const W*, W*,
-                  int64_t, int, hipStream_t);
-template <typename W>
-void launch_hub_argmax(const int32_t*, const W*, const int64_t*,
-                       const int32_t*, int, const double*, const int32_t*,
-                       const W*, const int64_t*, const W*, const int64_t*,
-                       int64_t, int32_t, double, double*, double*, int64_t*,
-                       int32_t*, int32_t*, double*, int32_t*, W*, int64_t*,
-                       W*, int64_t, hipStream_t);
-template <typename W>
-void launch_hub_refine_argmax(const int32_t*, const W*, const int64_t*,
-                              const int32_t*, int, const double*,
-                              const int32_t*, const W*, const W*,
-                              const int64_t*, int64_t, int32_t, double,
-                              double*, double*, int64_t*, int32_t*, int32_t*,
-                              double*, int32_t*, W*, const int32_t*,
-                              const int32_t*, hipStream_t);
-int hub_slices();
-template <typename W>
-void launch_apply_deltas(const int64_t*, const int64_t*, const W*, int64_t,
-                         int64_t, int64_t, int64_t*, W*, hipStream_t);
-template <typename W>
-void launch_recount(const int64_t*, const W*, int64_t, int64_t, int64_t,
-                    int64_t*, W*, hipStream_t);
-void launch_coloring_minmax(const int64_t*, const int32_t*, const int64_t*,
-                            const bool*, const int64_t*, int64_t, int64_t,
-                            const int64_t*, int, int64_t*, int64_t*,
-                            hipStream_t);
-template <typename W, typename L>
-void launch_intra_weight(const int64_t*, const int32_t*, const W*, const L*,
-                         int64_t, int64_t, int64_t, W*, hipStream_t);
-int intra_weight_span();
-template <typename L>
-void launch_cc_hook(const int64_t*, const int32_t*, const L*, int64_t,
-                    int64_t, int64_t, int32_t*, int32_t*, hipStream_t);
-void launch_cc_compress(int32_t*, int64_t, hipStream_t);
-
-}  // namespace cuvite
-
 namespace {
 
-#define CHECK_DEV(t) TORCH_CHECK((t).is_cuda(), #t " must be on GPU")
-#define CHECK_CONT(t) TORCH_CHECK((t).is_contiguous(), #t " must be contiguous")
+// A tensor a kernel reads or writes: on the device and contiguous.
+#define CHECK_INPUT(t)                                            \
+  do {                                                            \
+    TORCH_CHECK((t).is_cuda(), #t " must be on GPU");             \
+    TORCH_CHECK((t).is_contiguous(), #t " must be contiguous");   \
+  } while (0)
+
+// Two-phase rocPRIM call: run(nullptr, bytes) stores the scratch size in
+// `bytes`, then run(temp, bytes) works with that much scratch, allocated as
+// a byte tensor beside `like`.
+template <typename F>
+void with_scratch(const at::Tensor& like, F run) {
+  size_t bytes = 0;
+  run(nullptr, bytes);
+  auto temp = at::empty({(int64_t)bytes}, like.options().dtype(at::kByte));
+  run(temp.data_ptr(), bytes);
+}
 
 // Optional second aggregate pair the move kernels account their targets in
 // (see account_target): both or neither, int64 sizes, degrees in the weight
@@ -114,8 +39,8 @@ void check_next(const c10::optional<at::Tensor>& next_size,
   TORCH_CHECK(next_size.has_value() == next_degree.has_value(),
               "next_size and next_degree go together");
   if (!next_size.has_value()) return;
-  CHECK_DEV(*next_size); CHECK_CONT(*next_size);
-  CHECK_DEV(*next_degree); CHECK_CONT(*next_degree);
+  CHECK_INPUT(*next_size);
+  CHECK_INPUT(*next_degree);
   TORCH_CHECK(next_size->scalar_type() == at::kLong,
               "next_size must be int64");
   TORCH_CHECK(next_degree->scalar_type() == weights.scalar_type(),
@@ -130,29 +55,42 @@ void check_local_gids(int64_t n_local, const at::Tensor& comm_gid) {
               "n_local must lie in [0, number of communities]");
 }
 
+// comm_size, the next_* pair and the bound arrays may be absent (null in
+// MoveArgs): see launch.h for who reads what.
 template <typename W>
 cuvite::MoveArgs<W> make_args(const at::Tensor& rowptr, const at::Tensor& tails,
                               const at::Tensor& weights,
                               const at::Tensor& curr_comm,
                               const at::Tensor& v_degree,
-                              const at::Tensor& comm_size,
+                              const c10::optional<at::Tensor>& comm_size,
                               const at::Tensor& comm_degree,
                               const at::Tensor& comm_gid, double constant,
                               at::Tensor& target, at::Tensor& cw,
                               int64_t gid_base, int64_t n_local,
                               const c10::optional<at::Tensor>& next_size,
-                              const c10::optional<at::Tensor>& next_degree) {
-  return cuvite::MoveArgs<W>{
-      rowptr.data_ptr<int64_t>(),   tails.data_ptr<int32_t>(),
-      weights.data_ptr<W>(),        curr_comm.data_ptr<int32_t>(),
-      v_degree.data_ptr<W>(),       comm_size.data_ptr<int64_t>(),
-      comm_degree.data_ptr<W>(),    comm_gid.data_ptr<int64_t>(),
-      constant,                     target.data_ptr<int32_t>(),
-      cw.data_ptr<W>(),             gid_base,
-      (int32_t)n_local,
-      next_size ? next_size->data_ptr<int64_t>() : nullptr,
-      next_degree ? next_degree->data_ptr<W>() : nullptr,
-      next_size ? next_size->numel() : 0};
+                              const c10::optional<at::Tensor>& next_degree,
+                              const int32_t* mover_bound,
+                              const int32_t* cand_bound) {
+  cuvite::MoveArgs<W> a{};
+  a.rowptr = rowptr.data_ptr<int64_t>();
+  a.tails = tails.data_ptr<int32_t>();
+  a.weights = weights.data_ptr<W>();
+  a.curr_comm = curr_comm.data_ptr<int32_t>();
+  a.v_degree = v_degree.data_ptr<W>();
+  a.comm_size = comm_size ? comm_size->data_ptr<int64_t>() : nullptr;
+  a.comm_degree = comm_degree.data_ptr<W>();
+  a.comm_gid = comm_gid.data_ptr<int64_t>();
+  a.constant = constant;
+  a.target = target.data_ptr<int32_t>();
+  a.cluster_weight = cw.data_ptr<W>();
+  a.gid_base = gid_base;
+  a.n_local = (int32_t)n_local;
+  a.next_size = next_size ? next_size->data_ptr<int64_t>() : nullptr;
+  a.next_degree = next_degree ? next_degree->data_ptr<W>() : nullptr;
+  a.n_next = next_size ? next_size->numel() : 0;
+  a.mover_bound = mover_bound;
+  a.cand_bound = cand_bound;
+  return a;
 }
 
 // Auxiliary stream and fork/join events of local_move, made once per device
@@ -192,22 +130,21 @@ ClassStream& class_stream(int device) {
 // seven kernels on the calling stream.
 //
 // With `mover_bound` / `cand_bound` (both or neither) the refine kernels run
-// instead: see refine_move below.
+// instead and `comm_size` is absent: see refine_move below.
 std::vector<at::Tensor> local_move_impl(
     at::Tensor rowptr, at::Tensor tails, at::Tensor weights,
-    at::Tensor curr_comm, at::Tensor v_degree, at::Tensor comm_size,
-    at::Tensor comm_degree, at::Tensor comm_gid, double constant,
-    std::vector<at::Tensor> vlists, int64_t gid_base, int64_t n_local,
-    c10::optional<at::Tensor> next_size,
+    at::Tensor curr_comm, at::Tensor v_degree,
+    c10::optional<at::Tensor> comm_size, at::Tensor comm_degree,
+    at::Tensor comm_gid, double constant, std::vector<at::Tensor> vlists,
+    int64_t gid_base, int64_t n_local, c10::optional<at::Tensor> next_size,
     c10::optional<at::Tensor> next_degree, bool class_streams,
     const int32_t* mover_bound, const int32_t* cand_bound,
     c10::optional<at::Tensor> out_target = c10::nullopt,
     c10::optional<at::Tensor> out_cw = c10::nullopt) {
-  const bool refine = mover_bound != nullptr;
-  CHECK_DEV(rowptr); CHECK_CONT(rowptr);
-  CHECK_DEV(tails); CHECK_CONT(tails);
-  CHECK_DEV(weights); CHECK_CONT(weights);
-  CHECK_DEV(curr_comm); CHECK_CONT(curr_comm);
+  CHECK_INPUT(rowptr);
+  CHECK_INPUT(tails);
+  CHECK_INPUT(weights);
+  CHECK_INPUT(curr_comm);
   TORCH_CHECK(tails.scalar_type() == at::kInt, "tails must be int32");
   TORCH_CHECK(curr_comm.scalar_type() == at::kInt, "curr_comm must be int32");
   TORCH_CHECK(vlists.size() == 7, "expected 7 degree-class vertex lists"
@@ -221,8 +158,8 @@ std::vector<at::Tensor> local_move_impl(
   at::Tensor target, cw;
   if (out_target.has_value()) {
     // caller's buffers: int32 [nv] and weight dtype [nv], contiguous
-    CHECK_DEV(*out_target); CHECK_CONT(*out_target);
-    CHECK_DEV(*out_cw); CHECK_CONT(*out_cw);
+    CHECK_INPUT(*out_target);
+    CHECK_INPUT(*out_cw);
     TORCH_CHECK(out_target->scalar_type() == at::kInt &&
                 out_target->numel() == nv &&
                 out_cw->scalar_type() == weights.scalar_type() &&
@@ -254,53 +191,17 @@ std::vector<at::Tensor> local_move_impl(
     auto args = make_args<W>(rowptr, tails, weights, curr_comm, v_degree,
                              comm_size, comm_degree, comm_gid, constant,
                              target, cw, gid_base, n_local, next_size,
-                             next_degree);
-    const int32_t* mbp = mover_bound;
-    const int32_t* cbp = cand_bound;
-    auto block_class = [&](int c) {
+                             next_degree, mover_bound, cand_bound);
+    auto run_class = [&](int c, hipStream_t st) {
       if (!vlists[c].numel()) return;
-      const int32_t* vl = vlists[c].data_ptr<int32_t>();
-      const int n = (int)vlists[c].numel();
-      hipStream_t st = block_stream;
-      if (refine) {
-        if (c == 4)
-          cuvite::launch_refine_block<W, 2048>(vl, n, args, mbp, cbp, st);
-        if (c == 5)
-          cuvite::launch_refine_block<W, 4096>(vl, n, args, mbp, cbp, st);
-        if (c == 6)
-          cuvite::launch_refine_block<W, 8192>(vl, n, args, mbp, cbp, st);
-        return;
-      }
-      if (c == 4) cuvite::launch_block<W, 2048>(vl, n, args, block_stream);
-      if (c == 5) cuvite::launch_block<W, 4096>(vl, n, args, block_stream);
-      if (c == 6) cuvite::launch_block<W, 8192>(vl, n, args, block_stream);
-    };
-    auto sub_class = [&](int c) {
-      if (!vlists[c].numel()) return;
-      const int32_t* vl = vlists[c].data_ptr<int32_t>();
-      const int n = (int)vlists[c].numel();
-      if (refine) {
-        hipStream_t st = stream;
-        if (c == 0)
-          cuvite::launch_refine_sub<W, 16, 32>(vl, n, args, mbp, cbp, st);
-        if (c == 1)
-          cuvite::launch_refine_sub<W, 64, 128>(vl, n, args, mbp, cbp, st);
-        if (c == 2)
-          cuvite::launch_refine_sub<W, 64, 512>(vl, n, args, mbp, cbp, st);
-        if (c == 3)
-          cuvite::launch_refine_sub<W, 64, 1024>(vl, n, args, mbp, cbp, st);
-        return;
-      }
-      if (c == 0) cuvite::launch_sub<W, 16, 32>(vl, n, args, stream);
-      if (c == 1) cuvite::launch_sub<W, 64, 128>(vl, n, args, stream);
-      if (c == 2) cuvite::launch_sub<W, 64, 512>(vl, n, args, stream);
-      if (c == 3) cuvite::launch_sub<W, 64, 1024>(vl, n, args, stream);
+      cuvite::launch_class<W>(c, vlists[c].data_ptr<int32_t>(),
+                              (int)vlists[c].numel(), args, st);
     };
     if (fork)
-      for (int c : {6, 5, 4}) block_class(c);
-    for (int c : {0, 1, 2, 3}) sub_class(c);
+      for (int c : {6, 5, 4}) run_class(c, block_stream);
+    for (int c : {0, 1, 2, 3}) run_class(c, stream);
     if (!fork)
-      for (int c : {4, 5, 6}) block_class(c);
+      for (int c : {4, 5, 6}) run_class(c, stream);
   });
   if (fork) {
     C10_HIP_CHECK(hipEventRecord(cs->join, cs->stream));
@@ -328,8 +229,8 @@ std::vector<at::Tensor> local_move(
 // (bound id of a dense community that may be joined this round, else -1).
 void check_bounds(const at::Tensor& mover_bound, const at::Tensor& cand_bound,
                   int64_t nv, const at::Tensor& comm_degree) {
-  CHECK_DEV(mover_bound); CHECK_CONT(mover_bound);
-  CHECK_DEV(cand_bound); CHECK_CONT(cand_bound);
+  CHECK_INPUT(mover_bound);
+  CHECK_INPUT(cand_bound);
   TORCH_CHECK(mover_bound.scalar_type() == at::kInt &&
               cand_bound.scalar_type() == at::kInt,
               "mover_bound / cand_bound must be int32");
@@ -352,18 +253,17 @@ std::vector<at::Tensor> refine_move(
     int64_t n_local, bool class_streams,
     c10::optional<at::Tensor> out_target, c10::optional<at::Tensor> out_cw) {
   check_bounds(mover_bound, cand_bound, rowptr.numel() - 1, comm_degree);
-  // comm_size is not read by the refine kernels; comm_gid stands in for the
-  // argument (same dtype)
+  // comm_size is not read by the refine kernels
   return local_move_impl(rowptr, tails, weights, curr_comm, v_degree,
-                         comm_gid, comm_degree, comm_gid, constant, vlists,
+                         c10::nullopt, comm_degree, comm_gid, constant, vlists,
                          gid_base, n_local, c10::nullopt, c10::nullopt,
                          class_streams, mover_bound.data_ptr<int32_t>(),
                          cand_bound.data_ptr<int32_t>(), out_target, out_cw);
 }
 
 at::Tensor modularity_parts(at::Tensor cluster_weight, at::Tensor comm_degree) {
-  CHECK_DEV(cluster_weight); CHECK_CONT(cluster_weight);
-  CHECK_DEV(comm_degree); CHECK_CONT(comm_degree);
+  CHECK_INPUT(cluster_weight);
+  CHECK_INPUT(comm_degree);
   TORCH_CHECK(cluster_weight.numel() == comm_degree.numel());
   auto out = at::zeros({2}, cluster_weight.options().dtype(at::kDouble));
   auto stream = at::hip::getCurrentHIPStream().stream();
@@ -378,9 +278,9 @@ at::Tensor modularity_parts(at::Tensor cluster_weight, at::Tensor comm_degree) {
 }
 
 void scatter_add_(at::Tensor out, at::Tensor idx, at::Tensor val) {
-  CHECK_DEV(out); CHECK_CONT(out);
-  CHECK_DEV(idx); CHECK_CONT(idx);
-  CHECK_DEV(val); CHECK_CONT(val);
+  CHECK_INPUT(out);
+  CHECK_INPUT(idx);
+  CHECK_INPUT(val);
   TORCH_CHECK(idx.scalar_type() == at::kLong, "idx must be int64");
   TORCH_CHECK(idx.numel() == val.numel(), "idx/val length mismatch");
   TORCH_CHECK(out.scalar_type() == val.scalar_type(), "dtype mismatch");
@@ -397,9 +297,9 @@ void scatter_add_(at::Tensor out, at::Tensor idx, at::Tensor val) {
 std::vector<at::Tensor> csr_from_edges(int64_t nv, int64_t base,
                                        at::Tensor src, at::Tensor dst,
                                        at::Tensor w) {
-  CHECK_DEV(src); CHECK_CONT(src);
-  CHECK_DEV(dst); CHECK_CONT(dst);
-  CHECK_DEV(w); CHECK_CONT(w);
+  CHECK_INPUT(src);
+  CHECK_INPUT(dst);
+  CHECK_INPUT(w);
   TORCH_CHECK(src.scalar_type() == at::kLong && dst.scalar_type() == at::kLong,
               "src/dst must be int64");
   const int64_t ne = src.numel();
@@ -432,21 +332,20 @@ std::vector<at::Tensor> csr_from_edges(int64_t nv, int64_t base,
 // eoffs: int64 [nhub + 1] segment offsets into tails_flat / weights_flat.
 // Returns per-hub (target, wcc); with next_size / next_degree the hubs are
 // also accounted in that aggregate pair.
-// With mover_bound / cand_bound the refine argmax kernels run
-// (hub_refine_moves).
+// With mover_bound / cand_bound the refine argmax kernels run and comm_size
+// is absent (hub_refine_moves).
 std::vector<at::Tensor> hub_moves_impl(
     at::Tensor tails_flat, at::Tensor weights_flat, at::Tensor eoffs,
     at::Tensor hubs_i32, at::Tensor hub_self, at::Tensor curr_comm,
-    at::Tensor v_degree, at::Tensor comm_size, at::Tensor comm_degree,
-    at::Tensor comm_gid, double constant, int64_t gid_base, int64_t n_local,
-    c10::optional<at::Tensor> next_size,
+    at::Tensor v_degree, c10::optional<at::Tensor> comm_size,
+    at::Tensor comm_degree, at::Tensor comm_gid, double constant,
+    int64_t gid_base, int64_t n_local, c10::optional<at::Tensor> next_size,
     c10::optional<at::Tensor> next_degree, const int32_t* mover_bound,
     const int32_t* cand_bound) {
-  const bool refine = mover_bound != nullptr;
-  CHECK_DEV(tails_flat); CHECK_CONT(tails_flat);
-  CHECK_DEV(weights_flat); CHECK_CONT(weights_flat);
-  CHECK_DEV(eoffs); CHECK_CONT(eoffs);
-  CHECK_DEV(hubs_i32); CHECK_CONT(hubs_i32);
+  CHECK_INPUT(tails_flat);
+  CHECK_INPUT(weights_flat);
+  CHECK_INPUT(eoffs);
+  CHECK_INPUT(hubs_i32);
   check_local_gids(n_local, comm_gid);
   check_next(next_size, next_degree, weights_flat);
   TORCH_CHECK(tails_flat.scalar_type() == at::kInt);
@@ -476,20 +375,13 @@ std::vector<at::Tensor> hub_moves_impl(
                                keys.data_ptr<int32_t>(), stream);
     auto keys2 = at::empty({n}, tails_flat.options());
     auto vals2 = at::empty({n}, weights_flat.options());
-    size_t bytes = 0;
-    cuvite::segsort_pairs<W>(nullptr, &bytes, keys.data_ptr<int32_t>(),
-                             keys2.data_ptr<int32_t>(),
-                             weights_flat.data_ptr<W>(), vals2.data_ptr<W>(),
-                             n, nhub, eoffs.data_ptr<int64_t>(), end_bit,
-                             stream);
-    auto temp = at::empty({(int64_t)bytes},
-                          tails_flat.options().dtype(at::kByte));
-    cuvite::segsort_pairs<W>(temp.data_ptr(), &bytes,
-                             keys.data_ptr<int32_t>(),
-                             keys2.data_ptr<int32_t>(),
-                             weights_flat.data_ptr<W>(), vals2.data_ptr<W>(),
-                             n, nhub, eoffs.data_ptr<int64_t>(), end_bit,
-                             stream);
+    with_scratch(tails_flat, [&](void* temp, size_t& bytes) {
+      cuvite::segsort_pairs<W>(temp, &bytes, keys.data_ptr<int32_t>(),
+                               keys2.data_ptr<int32_t>(),
+                               weights_flat.data_ptr<W>(),
+                               vals2.data_ptr<W>(), n, nhub,
+                               eoffs.data_ptr<int64_t>(), end_bit, stream);
+    });
     const int64_t nslice = (int64_t)nhub * cuvite::hub_slices();
     auto f64 = eoffs.options().dtype(at::kDouble);
     auto p_wcc = at::empty({nslice}, f64);
@@ -498,34 +390,35 @@ std::vector<at::Tensor> hub_moves_impl(
     auto p_dense = at::empty({nslice}, tails_flat.options());
     auto r_key = at::empty({2 * nslice}, tails_flat.options());
     auto r_sum = at::empty({2 * nslice}, f64);
-    if (refine) {
-      cuvite::launch_hub_refine_argmax<W>(
-          keys2.data_ptr<int32_t>(), vals2.data_ptr<W>(),
-          eoffs.data_ptr<int64_t>(), hubs_i32.data_ptr<int32_t>(), nhub,
-          hub_self.data_ptr<double>(), curr_comm.data_ptr<int32_t>(),
-          v_degree.data_ptr<W>(), comm_degree.data_ptr<W>(),
-          comm_gid.data_ptr<int64_t>(), gid_base, (int32_t)n_local, constant,
-          p_wcc.data_ptr<double>(), p_gain.data_ptr<double>(),
-          p_gid.data_ptr<int64_t>(), p_dense.data_ptr<int32_t>(),
-          r_key.data_ptr<int32_t>(), r_sum.data_ptr<double>(),
-          target_hub.data_ptr<int32_t>(), cw_hub.data_ptr<W>(), mover_bound,
-          cand_bound, stream);
-      return;
-    }
-    cuvite::launch_hub_argmax<W>(
-        keys2.data_ptr<int32_t>(), vals2.data_ptr<W>(),
-        eoffs.data_ptr<int64_t>(), hubs_i32.data_ptr<int32_t>(), nhub,
-        hub_self.data_ptr<double>(), curr_comm.data_ptr<int32_t>(),
-        v_degree.data_ptr<W>(), comm_size.data_ptr<int64_t>(),
-        comm_degree.data_ptr<W>(), comm_gid.data_ptr<int64_t>(), gid_base,
-        (int32_t)n_local, constant, p_wcc.data_ptr<double>(),
-        p_gain.data_ptr<double>(), p_gid.data_ptr<int64_t>(),
-        p_dense.data_ptr<int32_t>(), r_key.data_ptr<int32_t>(),
-        r_sum.data_ptr<double>(), target_hub.data_ptr<int32_t>(),
-        cw_hub.data_ptr<W>(),
-        next_size ? next_size->data_ptr<int64_t>() : nullptr,
-        next_degree ? next_degree->data_ptr<W>() : nullptr,
-        next_size ? next_size->numel() : 0, stream);
+    cuvite::HubArgs<W> h{};
+    h.keys = keys2.data_ptr<int32_t>();
+    h.vals = vals2.data_ptr<W>();
+    h.eoffs = eoffs.data_ptr<int64_t>();
+    h.hubs = hubs_i32.data_ptr<int32_t>();
+    h.nhub = nhub;
+    h.hub_self = hub_self.data_ptr<double>();
+    h.curr_comm = curr_comm.data_ptr<int32_t>();
+    h.v_degree = v_degree.data_ptr<W>();
+    h.comm_size = comm_size ? comm_size->data_ptr<int64_t>() : nullptr;
+    h.comm_degree = comm_degree.data_ptr<W>();
+    h.comm_gid = comm_gid.data_ptr<int64_t>();
+    h.gid_base = gid_base;
+    h.n_local = (int32_t)n_local;
+    h.constant = constant;
+    h.p_wcc = p_wcc.data_ptr<double>();
+    h.p_gain = p_gain.data_ptr<double>();
+    h.p_gid = p_gid.data_ptr<int64_t>();
+    h.p_dense = p_dense.data_ptr<int32_t>();
+    h.r_key = r_key.data_ptr<int32_t>();
+    h.r_sum = r_sum.data_ptr<double>();
+    h.target_hub = target_hub.data_ptr<int32_t>();
+    h.cw_hub = cw_hub.data_ptr<W>();
+    h.next_size = next_size ? next_size->data_ptr<int64_t>() : nullptr;
+    h.next_degree = next_degree ? next_degree->data_ptr<W>() : nullptr;
+    h.n_next = next_size ? next_size->numel() : 0;
+    h.mover_bound = mover_bound;
+    h.cand_bound = cand_bound;
+    cuvite::launch_hub_argmax<W>(h, stream);
   });
   C10_HIP_CHECK(hipGetLastError());
   return {target_hub, cw_hub};
@@ -554,8 +447,8 @@ std::vector<at::Tensor> hub_refine_moves(
     int64_t gid_base, int64_t n_local) {
   check_bounds(mover_bound, cand_bound, v_degree.numel(), comm_degree);
   return hub_moves_impl(tails_flat, weights_flat, eoffs, hubs_i32, hub_self,
-                        curr_comm, v_degree, comm_gid, comm_degree, comm_gid,
-                        constant, gid_base, n_local, c10::nullopt,
+                        curr_comm, v_degree, c10::nullopt, comm_degree,
+                        comm_gid, constant, gid_base, n_local, c10::nullopt,
                         c10::nullopt, mover_bound.data_ptr<int32_t>(),
                         cand_bound.data_ptr<int32_t>());
 }
@@ -563,10 +456,10 @@ std::vector<at::Tensor> hub_refine_moves(
 // Fresh world-1 recount of the community aggregates (see recount_kernel).
 void recount_(at::Tensor labels, at::Tensor v_degree, int64_t base,
               at::Tensor size, at::Tensor degree) {
-  CHECK_DEV(labels); CHECK_CONT(labels);
-  CHECK_DEV(v_degree); CHECK_CONT(v_degree);
-  CHECK_DEV(size); CHECK_CONT(size);
-  CHECK_DEV(degree); CHECK_CONT(degree);
+  CHECK_INPUT(labels);
+  CHECK_INPUT(v_degree);
+  CHECK_INPUT(size);
+  CHECK_INPUT(degree);
   TORCH_CHECK(labels.scalar_type() == at::kLong);
   TORCH_CHECK(size.scalar_type() == at::kLong);
   TORCH_CHECK(labels.numel() == v_degree.numel());
@@ -589,8 +482,8 @@ void recount_(at::Tensor labels, at::Tensor v_degree, int64_t base,
 // std::maps on the host there).
 std::vector<at::Tensor> sort_reduce_pairs(at::Tensor key, at::Tensor val,
                                           int64_t end_bit) {
-  CHECK_DEV(key); CHECK_CONT(key);
-  CHECK_DEV(val); CHECK_CONT(val);
+  CHECK_INPUT(key);
+  CHECK_INPUT(val);
   TORCH_CHECK(key.scalar_type() == at::kLong, "key must be int64");
   TORCH_CHECK(key.numel() == val.numel());
   const int64_t n = key.numel();
@@ -604,28 +497,18 @@ std::vector<at::Tensor> sort_reduce_pairs(at::Tensor key, at::Tensor val,
     using W = scalar_t;
     auto keys2 = at::empty({n}, key.options());
     auto vals2 = at::empty({n}, val.options());
-    size_t bytes = 0;
-    cuvite::sort_pairs64<W>(nullptr, &bytes, key.data_ptr<int64_t>(),
-                            keys2.data_ptr<int64_t>(), val.data_ptr<W>(),
-                            vals2.data_ptr<W>(), n, (int)end_bit, stream);
-    auto temp = at::empty({(int64_t)bytes}, key.options().dtype(at::kByte));
-    cuvite::sort_pairs64<W>(temp.data_ptr(), &bytes, key.data_ptr<int64_t>(),
-                            keys2.data_ptr<int64_t>(), val.data_ptr<W>(),
-                            vals2.data_ptr<W>(), n, (int)end_bit, stream);
-    size_t bytes2 = 0;
-    cuvite::reduce_by_key64<W>(nullptr, &bytes2, keys2.data_ptr<int64_t>(),
-                               vals2.data_ptr<W>(), n,
-                               uniq.data_ptr<int64_t>(), sums.data_ptr<W>(),
-                               (unsigned int*)cnt.data_ptr<int32_t>(),
-                               stream);
-    auto temp2 = at::empty({(int64_t)bytes2},
-                           key.options().dtype(at::kByte));
-    cuvite::reduce_by_key64<W>(temp2.data_ptr(), &bytes2,
-                               keys2.data_ptr<int64_t>(),
-                               vals2.data_ptr<W>(), n,
-                               uniq.data_ptr<int64_t>(), sums.data_ptr<W>(),
-                               (unsigned int*)cnt.data_ptr<int32_t>(),
-                               stream);
+    with_scratch(key, [&](void* temp, size_t& bytes) {
+      cuvite::sort_pairs64<W>(temp, &bytes, key.data_ptr<int64_t>(),
+                              keys2.data_ptr<int64_t>(), val.data_ptr<W>(),
+                              vals2.data_ptr<W>(), n, (int)end_bit, stream);
+    });
+    with_scratch(key, [&](void* temp, size_t& bytes) {
+      cuvite::reduce_by_key64<W>(temp, &bytes, keys2.data_ptr<int64_t>(),
+                                 vals2.data_ptr<W>(), n,
+                                 uniq.data_ptr<int64_t>(), sums.data_ptr<W>(),
+                                 (unsigned int*)cnt.data_ptr<int32_t>(),
+                                 stream);
+    });
   });
   C10_HIP_CHECK(hipGetLastError());
   return {uniq, sums, cnt};
@@ -634,11 +517,11 @@ std::vector<at::Tensor> sort_reduce_pairs(at::Tensor key, at::Tensor val,
 void apply_deltas_(at::Tensor target, at::Tensor curr, at::Tensor v_degree,
                    int64_t base, int64_t bound, at::Tensor local_size,
                    at::Tensor local_degree) {
-  CHECK_DEV(target); CHECK_CONT(target);
-  CHECK_DEV(curr); CHECK_CONT(curr);
-  CHECK_DEV(v_degree); CHECK_CONT(v_degree);
-  CHECK_DEV(local_size); CHECK_CONT(local_size);
-  CHECK_DEV(local_degree); CHECK_CONT(local_degree);
+  CHECK_INPUT(target);
+  CHECK_INPUT(curr);
+  CHECK_INPUT(v_degree);
+  CHECK_INPUT(local_size);
+  CHECK_INPUT(local_degree);
   TORCH_CHECK(target.scalar_type() == at::kLong &&
               curr.scalar_type() == at::kLong, "labels must be int64");
   TORCH_CHECK(local_size.scalar_type() == at::kLong);
@@ -662,11 +545,11 @@ std::vector<at::Tensor> coloring_minmax(at::Tensor rowptr, at::Tensor tails,
                                         at::Tensor uncolored,
                                         at::Tensor colors, int64_t base,
                                         at::Tensor seeds) {
-  CHECK_DEV(rowptr); CHECK_CONT(rowptr);
-  CHECK_DEV(tails); CHECK_CONT(tails);
-  CHECK_DEV(gid_all); CHECK_CONT(gid_all);
-  CHECK_DEV(uncolored); CHECK_CONT(uncolored);
-  CHECK_DEV(colors); CHECK_CONT(colors);
+  CHECK_INPUT(rowptr);
+  CHECK_INPUT(tails);
+  CHECK_INPUT(gid_all);
+  CHECK_INPUT(uncolored);
+  CHECK_INPUT(colors);
   TORCH_CHECK(tails.scalar_type() == at::kInt);
   TORCH_CHECK(uncolored.scalar_type() == at::kBool);
   TORCH_CHECK(seeds.scalar_type() == at::kLong && seeds.is_cuda());
@@ -686,8 +569,8 @@ std::vector<at::Tensor> coloring_minmax(at::Tensor rowptr, at::Tensor tails,
 }
 
 at::Tensor row_sum(at::Tensor rowptr, at::Tensor weights) {
-  CHECK_DEV(rowptr); CHECK_CONT(rowptr);
-  CHECK_DEV(weights); CHECK_CONT(weights);
+  CHECK_INPUT(rowptr);
+  CHECK_INPUT(weights);
   const int64_t nv = rowptr.numel() - 1;
   auto out = at::empty({nv}, weights.options());
   auto stream = at::hip::getCurrentHIPStream().stream();
@@ -704,10 +587,10 @@ at::Tensor row_sum(at::Tensor rowptr, at::Tensor weights) {
 // (see intra_weight_kernel). labels: int32 or int64, [nv + ng].
 at::Tensor intra_weight(at::Tensor rowptr, at::Tensor tails,
                         at::Tensor weights, at::Tensor labels) {
-  CHECK_DEV(rowptr); CHECK_CONT(rowptr);
-  CHECK_DEV(tails); CHECK_CONT(tails);
-  CHECK_DEV(weights); CHECK_CONT(weights);
-  CHECK_DEV(labels); CHECK_CONT(labels);
+  CHECK_INPUT(rowptr);
+  CHECK_INPUT(tails);
+  CHECK_INPUT(weights);
+  CHECK_INPUT(labels);
   TORCH_CHECK(rowptr.scalar_type() == at::kLong, "rowptr must be int64");
   TORCH_CHECK(rowptr.numel() >= 1, "rowptr must have nv + 1 entries");
   TORCH_CHECK(tails.scalar_type() == at::kInt, "tails must be int32");
@@ -744,9 +627,9 @@ at::Tensor intra_weight(at::Tensor rowptr, at::Tensor tails,
 std::tuple<at::Tensor, int64_t> cc_components(at::Tensor rowptr,
                                               at::Tensor tails,
                                               at::Tensor labels) {
-  CHECK_DEV(rowptr); CHECK_CONT(rowptr);
-  CHECK_DEV(tails); CHECK_CONT(tails);
-  CHECK_DEV(labels); CHECK_CONT(labels);
+  CHECK_INPUT(rowptr);
+  CHECK_INPUT(tails);
+  CHECK_INPUT(labels);
   TORCH_CHECK(rowptr.scalar_type() == at::kLong, "rowptr must be int64");
   TORCH_CHECK(rowptr.numel() >= 1, "rowptr must have nv + 1 entries");
   TORCH_CHECK(tails.scalar_type() == at::kInt, "tails must be int32");

@@ -69,6 +69,13 @@
 // (checked where its gain is folded into the argmax, one 4-byte gather per
 // distinct candidate), and there is neither singleton guard nor aggregate
 // accounting.
+//
+// Host interface: launch.h holds the argument structs (MoveArgs, HubArgs) and
+// the declaration of every launcher defined at the end of this file. The
+// degree classes are launched by launch_class, one kernel instantiation per
+// row of CLASS_TABLE below.
+
+#include "launch.h"
 
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
@@ -80,6 +87,19 @@
 #define DEV_INLINE __device__ __forceinline__
 
 namespace cuvite {
+
+// The degree classes of the header comment as code, and the only place their
+// geometry is written. lanes > 0: lv_move_sub with that many lanes per
+// vertex; lanes == 0: lv_move_block, one block per vertex. cap: LDS table
+// slots per vertex. Every class runs CLASS_BLOCK threads per block.
+struct ClassGeometry {
+  int lanes, cap;
+};
+constexpr ClassGeometry CLASS_TABLE[] = {
+    {16, 32},  {64, 128}, {64, 512}, {64, 1024},  // classes 0-3
+    {0, 2048}, {0, 4096}, {0, 8192}};             // classes 4-6
+constexpr int NUM_CLASSES = sizeof(CLASS_TABLE) / sizeof(CLASS_TABLE[0]);
+constexpr int CLASS_BLOCK = 256;
 
 static constexpr int32_t EMPTY_KEY = -1;
 
@@ -112,6 +132,15 @@ DEV_INLINE void best_combine(Best& a, double g, int64_t gid, int32_t dense) {
     a.gid = gid;
     a.dense = dense;
   }
+}
+
+// Modularity gain (up to a constant factor) of moving a vertex of degree
+// vdeg from its community (weight eix into it, degree ax without the vertex)
+// to community y (weight eiy, degree ay). The one expression and operand
+// order every move kernel uses, so equal inputs give equal bits.
+DEV_INLINE double move_gain(double eiy, double eix, double vdeg, double ay,
+                            double ax, double constant) {
+  return 2.0 * (eiy - eix) - 2.0 * vdeg * (ay - ax) * constant;
 }
 
 // Global id of dense community y. Locally owned communities occupy the dense
@@ -240,7 +269,7 @@ DEV_INLINE void scan_slots(const int32_t* keys, const W* vals, int cap,
     if (REFINE && cand_bound[y] != mb) continue;
     double eiy = (double)vals[s];
     double ay = (double)comm_degree[y];
-    double g = 2.0 * (eiy - eix) - 2.0 * vdeg * (ay - ax) * constant;
+    double g = move_gain(eiy, eix, vdeg, ay, ax, constant);
     best_combine(best, g, gid_of(comm_gid, gid_base, n_local, y), y);
   }
 }
@@ -693,6 +722,22 @@ DEV_INLINE int64_t row_of_edge(const int64_t* __restrict__ rowptr, int64_t lo,
   return lo;
 }
 
+// Wave-uniform row range [rlo, rhi] that holds the rows of the edges
+// [s0, s1): the first row by a binary search over all of rowptr, the last by
+// a gallop out of the first (rhi may overshoot the true last row).
+DEV_INLINE void span_row_range(const int64_t* __restrict__ rowptr, int64_t nv,
+                               int64_t s0, int64_t s1, int64_t& rlo,
+                               int64_t& rhi) {
+  rlo = row_of_edge(rowptr, 0, nv - 1, s0);
+  rhi = rlo;
+  int64_t step = 1;
+  while (rhi + step < nv && rowptr[rhi + step] < s1) {
+    rhi += step;
+    step <<= 1;
+  }
+  rhi = (rhi + step - 1 < nv - 1) ? rhi + step - 1 : nv - 1;
+}
+
 template <typename W, typename L, int BLOCK>
 __global__ __launch_bounds__(BLOCK) void intra_weight_kernel(
     const int64_t* __restrict__ rowptr, const int32_t* __restrict__ tails,
@@ -707,14 +752,8 @@ __global__ __launch_bounds__(BLOCK) void intra_weight_kernel(
        s += sstride) {
     const int64_t s0 = s * IW_SPAN;
     const int64_t s1 = (s0 + IW_SPAN < ne) ? s0 + IW_SPAN : ne;
-    // wave-uniform row range of the span
-    int64_t rlo = row_of_edge(rowptr, 0, nv - 1, s0);
-    int64_t rhi = rlo, step = 1;
-    while (rhi + step < nv && rowptr[rhi + step] < s1) {
-      rhi += step;
-      step <<= 1;
-    }
-    rhi = (rhi + step - 1 < nv - 1) ? rhi + step - 1 : nv - 1;
+    int64_t rlo, rhi;
+    span_row_range(rowptr, nv, s0, s1, rlo, rhi);
 
     double carry_val = 0.0;
     int32_t carry_row = -1;  // row whose run continues from the last chunk
@@ -833,14 +872,8 @@ __global__ __launch_bounds__(BLOCK) void cc_hook_kernel(
        s += sstride) {
     const int64_t s0 = s * IW_SPAN;
     const int64_t s1 = (s0 + IW_SPAN < ne) ? s0 + IW_SPAN : ne;
-    // wave-uniform row range of the span
-    int64_t rlo = row_of_edge(rowptr, 0, nv - 1, s0);
-    int64_t rhi = rlo, step = 1;
-    while (rhi + step < nv && rowptr[rhi + step] < s1) {
-      rhi += step;
-      step <<= 1;
-    }
-    rhi = (rhi + step - 1 < nv - 1) ? rhi + step - 1 : nv - 1;
+    int64_t rlo, rhi;
+    span_row_range(rowptr, nv, s0, s1, rlo, rhi);
 
     for (int64_t c = s0; c < s1; c += (int64_t)IW_PIPE * 64) {
       int32_t t[IW_PIPE];
@@ -952,7 +985,7 @@ __global__ void gather_comm_kernel(const int32_t* __restrict__ tails_flat,
 //
 // Every sum is fp64 in an order fixed by the slice layout (no float atomics
 // on weights), rounded to the weight type once per run like the LDS tables'
-// entries; gains use the class kernels' expression and operand order.
+// entries; gains come from move_gain, like the class kernels'.
 // ---------------------------------------------------------------------------
 
 constexpr int HUB_SLICES = 32;   // 2 records per slice = one per final lane
@@ -1108,8 +1141,7 @@ __global__ __launch_bounds__(BLOCK) void hub_slice_kernel(
         } else if (kk != cc && (!REFINE || cand_bound[kk] == mb)) {
           const double eiy = (double)(W)val;
           const double ay = (double)comm_degree[kk];
-          const double g =
-              2.0 * (eiy - eix) - 2.0 * vdeg * (ay - ax) * constant;
+          const double g = move_gain(eiy, eix, vdeg, ay, ax, constant);
           best_combine(best, g, gid_of(comm_gid, gid_base, n_local, kk), kk);
         }
       }
@@ -1191,7 +1223,7 @@ __global__ __launch_bounds__(BLOCK) void hub_final_kernel(
   if (leader && key != cc && (!REFINE || cand_bound[key] == mb)) {
     const double eiy = (double)(W)total;
     const double ay = (double)comm_degree[key];
-    const double g = 2.0 * (eiy - eix) - 2.0 * vdeg * (ay - ax) * constant;
+    const double g = move_gain(eiy, eix, vdeg, ay, ax, constant);
     best_combine(best, g, gid_of(comm_gid, gid_base, n_local, key), key);
   }
   best_reduce<64>(best);
@@ -1215,145 +1247,58 @@ static int grid_for(int64_t n, int block) {
   return (int)(g < 1 ? 1 : (g > 65535 ? 65535 : g));
 }
 
+// One row of CLASS_TABLE. The sub and the block kernel take the same
+// parameters; they differ in the vertices a block serves (GROUPS).
+template <typename W, int C, bool REFINE>
+static auto class_kernel() {
+  constexpr ClassGeometry g = CLASS_TABLE[C];
+  if constexpr (g.lanes != 0)
+    return lv_move_sub<W, g.lanes, g.cap, CLASS_BLOCK, REFINE>;
+  else
+    return lv_move_block<W, g.cap, CLASS_BLOCK, REFINE>;
+}
 
-template <typename W>
-struct MoveArgs {
-  const int64_t* rowptr;
-  const int32_t* tails;
-  const W* weights;
-  const int32_t* curr_comm;
-  const W* v_degree;
-  const int64_t* comm_size;
-  const W* comm_degree;
-  const int64_t* comm_gid;
-  double constant;
-  int32_t* target;
-  W* cluster_weight;
-  int64_t gid_base;     // gid(y) = gid_base + y for y < n_local (gid_of)
-  int32_t n_local;      // 0: every gid is read from comm_gid
-  int64_t* next_size;   // fused aggregates (account_target); null = off
-  W* next_degree;
-  int64_t n_next;       // length of next_size / next_degree
-};
+// Walks CLASS_TABLE at compile time down to row c and launches its kernel.
+template <typename W, bool REFINE, int C = 0>
+static void launch_class_row(int c, const int32_t* vlist, int nlist,
+                             const MoveArgs<W>& a, hipStream_t stream) {
+  if constexpr (C < NUM_CLASSES) {
+    if (c != C)
+      return launch_class_row<W, REFINE, C + 1>(c, vlist, nlist, a, stream);
+    constexpr ClassGeometry g = CLASS_TABLE[C];
+    constexpr int GROUPS = g.lanes != 0 ? CLASS_BLOCK / g.lanes : 1;
+    const int grid = (nlist + GROUPS - 1) / GROUPS;
+    const size_t shmem =
+        (size_t)GROUPS * g.cap * (sizeof(W) + sizeof(int32_t));
+    auto kern = class_kernel<W, C, REFINE>();
+    if (shmem > 65536)
+      (void)hipFuncSetAttribute((const void*)kern,
+                                hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)shmem);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(CLASS_BLOCK), shmem, stream,
+                       vlist, nlist, a.rowptr, a.tails, a.weights,
+                       a.curr_comm, a.v_degree, a.comm_size, a.comm_degree,
+                       a.comm_gid, a.constant, a.target, a.cluster_weight,
+                       a.gid_base, a.n_local, a.next_size, a.next_degree,
+                       a.n_next, a.mover_bound, a.cand_bound);
+  }
+}
 
 // REFINE = false: the plain kernels (the bound arrays are null and not
-// read); REFINE = true: the refine kernels, same grids and tables.
-template <typename W, int LANES, int CAP, bool REFINE>
-static void launch_sub_impl(const int32_t* vlist, int nlist,
-                            const MoveArgs<W>& a, const int32_t* mover_bound,
-                            const int32_t* cand_bound, hipStream_t stream) {
-  constexpr int BLOCK = 256;
-  constexpr int GROUPS = BLOCK / LANES;
-  const int grid = (nlist + GROUPS - 1) / GROUPS;
-  const size_t shmem = (size_t)GROUPS * CAP * (sizeof(W) + sizeof(int32_t));
-  auto kern = lv_move_sub<W, LANES, CAP, BLOCK, REFINE>;
-  if (shmem > 65536)
-    (void)hipFuncSetAttribute((const void*)kern,
-                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)shmem);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), shmem, stream, vlist,
-                     nlist, a.rowptr, a.tails, a.weights, a.curr_comm,
-                     a.v_degree, a.comm_size, a.comm_degree, a.comm_gid,
-                     a.constant, a.target, a.cluster_weight, a.gid_base,
-                     a.n_local, a.next_size, a.next_degree, a.n_next,
-                     mover_bound, cand_bound);
+// read); REFINE = true: the refine kernels, same grids and tables. A class
+// outside the table launches nothing.
+template <typename W>
+void launch_class(int c, const int32_t* vlist, int nlist,
+                  const MoveArgs<W>& args, hipStream_t stream) {
+  if (args.mover_bound != nullptr)
+    launch_class_row<W, true>(c, vlist, nlist, args, stream);
+  else
+    launch_class_row<W, false>(c, vlist, nlist, args, stream);
 }
-
-template <typename W, int CAP, bool REFINE>
-static void launch_block_impl(const int32_t* vlist, int nlist,
-                              const MoveArgs<W>& a,
-                              const int32_t* mover_bound,
-                              const int32_t* cand_bound, hipStream_t stream) {
-  constexpr int BLOCK = 256;
-  const size_t shmem = (size_t)CAP * (sizeof(W) + sizeof(int32_t));
-  auto kern = lv_move_block<W, CAP, BLOCK, REFINE>;
-  if (shmem > 65536)
-    (void)hipFuncSetAttribute((const void*)kern,
-                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)shmem);
-  hipLaunchKernelGGL(kern, dim3(nlist), dim3(BLOCK), shmem, stream, vlist,
-                     nlist, a.rowptr, a.tails, a.weights, a.curr_comm,
-                     a.v_degree, a.comm_size, a.comm_degree, a.comm_gid,
-                     a.constant, a.target, a.cluster_weight, a.gid_base,
-                     a.n_local, a.next_size, a.next_degree, a.n_next,
-                     mover_bound, cand_bound);
-}
-
-template <typename W, int LANES, int CAP>
-void launch_sub(const int32_t* vlist, int nlist, const MoveArgs<W>& a,
-                hipStream_t stream) {
-  launch_sub_impl<W, LANES, CAP, false>(vlist, nlist, a, nullptr, nullptr,
-                                        stream);
-}
-
-template <typename W, int CAP>
-void launch_block(const int32_t* vlist, int nlist, const MoveArgs<W>& a,
-                  hipStream_t stream) {
-  launch_block_impl<W, CAP, false>(vlist, nlist, a, nullptr, nullptr, stream);
-}
-
-// Refine round: a.comm_size and the next_* pair are not read.
-template <typename W, int LANES, int CAP>
-void launch_refine_sub(const int32_t* vlist, int nlist, const MoveArgs<W>& a,
-                       const int32_t* mover_bound, const int32_t* cand_bound,
-                       hipStream_t stream) {
-  launch_sub_impl<W, LANES, CAP, true>(vlist, nlist, a, mover_bound,
-                                       cand_bound, stream);
-}
-
-template <typename W, int CAP>
-void launch_refine_block(const int32_t* vlist, int nlist,
-                         const MoveArgs<W>& a, const int32_t* mover_bound,
-                         const int32_t* cand_bound, hipStream_t stream) {
-  launch_block_impl<W, CAP, true>(vlist, nlist, a, mover_bound, cand_bound,
-                                  stream);
-}
-
-#define INSTANTIATE_REFINE(W)                                                 \
-  template void launch_refine_sub<W, 16, 32>(                                 \
-      const int32_t*, int, const MoveArgs<W>&, const int32_t*,                \
-      const int32_t*, hipStream_t);                                           \
-  template void launch_refine_sub<W, 64, 128>(                                \
-      const int32_t*, int, const MoveArgs<W>&, const int32_t*,                \
-      const int32_t*, hipStream_t);                                           \
-  template void launch_refine_sub<W, 64, 512>(                                \
-      const int32_t*, int, const MoveArgs<W>&, const int32_t*,                \
-      const int32_t*, hipStream_t);                                           \
-  template void launch_refine_sub<W, 64, 1024>(                               \
-      const int32_t*, int, const MoveArgs<W>&, const int32_t*,                \
-      const int32_t*, hipStream_t);                                           \
-  template void launch_refine_block<W, 2048>(                                 \
-      const int32_t*, int, const MoveArgs<W>&, const int32_t*,                \
-      const int32_t*, hipStream_t);                                           \
-  template void launch_refine_block<W, 4096>(                                 \
-      const int32_t*, int, const MoveArgs<W>&, const int32_t*,                \
-      const int32_t*, hipStream_t);                                           \
-  template void launch_refine_block<W, 8192>(                                 \
-      const int32_t*, int, const MoveArgs<W>&, const int32_t*,                \
-      const int32_t*, hipStream_t);
-
-INSTANTIATE_REFINE(float)
-INSTANTIATE_REFINE(double)
-
-// explicit instantiations used by bindings.cpp
-#define INSTANTIATE(W)                                                        \
-  template void launch_sub<W, 16, 32>(const int32_t*, int, const MoveArgs<W>&,\
-                                      hipStream_t);                           \
-  template void launch_sub<W, 64, 128>(const int32_t*, int,                  \
-                                       const MoveArgs<W>&, hipStream_t);     \
-  template void launch_sub<W, 64, 512>(const int32_t*, int,                  \
-                                       const MoveArgs<W>&, hipStream_t);     \
-  template void launch_sub<W, 64, 1024>(const int32_t*, int,                 \
-                                        const MoveArgs<W>&, hipStream_t);    \
-  template void launch_block<W, 2048>(const int32_t*, int,                  \
-                                      const MoveArgs<W>&, hipStream_t);      \
-  template void launch_block<W, 4096>(const int32_t*, int,                  \
-                                      const MoveArgs<W>&, hipStream_t);      \
-  template void launch_block<W, 8192>(const int32_t*, int,                  \
-                                      const MoveArgs<W>&, hipStream_t);
-
-INSTANTIATE(float)
-INSTANTIATE(double)
+template void launch_class<float>(int, const int32_t*, int,
+                                  const MoveArgs<float>&, hipStream_t);
+template void launch_class<double>(int, const int32_t*, int,
+                                   const MoveArgs<double>&, hipStream_t);
 
 template <typename W>
 void launch_modularity(const W* cw, const W* cd, int64_t nv, double* out,
@@ -1474,93 +1419,43 @@ void launch_gather_comm(const int32_t* tails_flat, const int32_t* curr_comm,
                      stream, tails_flat, curr_comm, n, keys);
 }
 
-template <typename W>
-void launch_hub_argmax(const int32_t* keys, const W* vals,
-                       const int64_t* eoffs, const int32_t* hubs, int nhub,
-                       const double* hub_self, const int32_t* curr_comm,
-                       const W* v_degree, const int64_t* comm_size,
-                       const W* comm_degree, const int64_t* comm_gid,
-                       int64_t gid_base, int32_t n_local, double constant,
-                       double* p_wcc, double* p_gain, int64_t* p_gid,
-                       int32_t* p_dense, int32_t* r_key, double* r_sum,
-                       int32_t* target_hub, W* cw_hub, int64_t* next_size,
-                       W* next_degree, int64_t n_next, hipStream_t stream) {
-  if (nhub == 0) return;
+// The own-weight kernel is shared; the slice and final kernels are plain or
+// REFINE instantiations, chosen like the class kernels'.
+template <typename W, bool REFINE>
+static void launch_hub_argmax_impl(const HubArgs<W>& h, hipStream_t stream) {
   constexpr int BLOCK = 256;
   constexpr int WAVES = BLOCK / 64;
   static_assert(HUB_SLICES % WAVES == 0, "whole blocks per hub");
-  const dim3 slice_grid((uint32_t)nhub * (HUB_SLICES / WAVES));
+  const dim3 slice_grid((uint32_t)h.nhub * (HUB_SLICES / WAVES));
   hipLaunchKernelGGL((hub_own_weight_kernel<W, BLOCK>), slice_grid,
-                     dim3(BLOCK), 0, stream, keys, vals, eoffs, hubs, nhub,
-                     curr_comm, p_wcc);
-  const int32_t* no_bound = nullptr;
-  hipLaunchKernelGGL((hub_slice_kernel<W, BLOCK, false>), slice_grid,
-                     dim3(BLOCK), 0, stream, keys, vals, eoffs, hubs, nhub,
-                     hub_self, p_wcc, curr_comm, v_degree, comm_degree,
-                     comm_gid, gid_base, n_local, constant, p_gain, p_gid,
-                     p_dense, r_key, r_sum, no_bound, no_bound);
-  hipLaunchKernelGGL((hub_final_kernel<W, BLOCK, false>),
-                     dim3((nhub + WAVES - 1) / WAVES), dim3(BLOCK), 0, stream,
-                     hubs, nhub, hub_self, p_wcc, curr_comm, v_degree,
-                     comm_size, comm_degree, comm_gid, gid_base, n_local,
-                     constant, p_gain, p_gid, p_dense, r_key, r_sum,
-                     target_hub, cw_hub, next_size, next_degree, n_next,
-                     no_bound, no_bound);
+                     dim3(BLOCK), 0, stream, h.keys, h.vals, h.eoffs, h.hubs,
+                     h.nhub, h.curr_comm, h.p_wcc);
+  hipLaunchKernelGGL((hub_slice_kernel<W, BLOCK, REFINE>), slice_grid,
+                     dim3(BLOCK), 0, stream, h.keys, h.vals, h.eoffs, h.hubs,
+                     h.nhub, h.hub_self, h.p_wcc, h.curr_comm, h.v_degree,
+                     h.comm_degree, h.comm_gid, h.gid_base, h.n_local,
+                     h.constant, h.p_gain, h.p_gid, h.p_dense, h.r_key,
+                     h.r_sum, h.mover_bound, h.cand_bound);
+  hipLaunchKernelGGL((hub_final_kernel<W, BLOCK, REFINE>),
+                     dim3((h.nhub + WAVES - 1) / WAVES), dim3(BLOCK), 0,
+                     stream, h.hubs, h.nhub, h.hub_self, h.p_wcc, h.curr_comm,
+                     h.v_degree, h.comm_size, h.comm_degree, h.comm_gid,
+                     h.gid_base, h.n_local, h.constant, h.p_gain, h.p_gid,
+                     h.p_dense, h.r_key, h.r_sum, h.target_hub, h.cw_hub,
+                     h.next_size, h.next_degree, h.n_next, h.mover_bound,
+                     h.cand_bound);
 }
-#define INSTANTIATE_HUB(W)                                                    \
-  template void launch_hub_argmax<W>(                                         \
-      const int32_t*, const W*, const int64_t*, const int32_t*, int,          \
-      const double*, const int32_t*, const W*, const int64_t*, const W*,      \
-      const int64_t*, int64_t, int32_t, double, double*, double*, int64_t*,   \
-      int32_t*, int32_t*, double*, int32_t*, W*, int64_t*, W*, int64_t,       \
-      hipStream_t);
-INSTANTIATE_HUB(float)
-INSTANTIATE_HUB(double)
 
-// Refine variant of launch_hub_argmax: the own-weight kernel is shared, the
-// slice and final kernels are their REFINE instantiations.
 template <typename W>
-void launch_hub_refine_argmax(
-    const int32_t* keys, const W* vals, const int64_t* eoffs,
-    const int32_t* hubs, int nhub, const double* hub_self,
-    const int32_t* curr_comm, const W* v_degree, const W* comm_degree,
-    const int64_t* comm_gid, int64_t gid_base, int32_t n_local,
-    double constant, double* p_wcc, double* p_gain, int64_t* p_gid,
-    int32_t* p_dense, int32_t* r_key, double* r_sum, int32_t* target_hub,
-    W* cw_hub, const int32_t* mover_bound, const int32_t* cand_bound,
-    hipStream_t stream) {
-  if (nhub == 0) return;
-  constexpr int BLOCK = 256;
-  constexpr int WAVES = BLOCK / 64;
-  const dim3 slice_grid((uint32_t)nhub * (HUB_SLICES / WAVES));
-  hipLaunchKernelGGL((hub_own_weight_kernel<W, BLOCK>), slice_grid,
-                     dim3(BLOCK), 0, stream, keys, vals, eoffs, hubs, nhub,
-                     curr_comm, p_wcc);
-  hipLaunchKernelGGL((hub_slice_kernel<W, BLOCK, true>), slice_grid,
-                     dim3(BLOCK), 0, stream, keys, vals, eoffs, hubs, nhub,
-                     hub_self, p_wcc, curr_comm, v_degree, comm_degree,
-                     comm_gid, gid_base, n_local, constant, p_gain, p_gid,
-                     p_dense, r_key, r_sum, mover_bound, cand_bound);
-  const int64_t* no_size = nullptr;
-  int64_t* no_next_size = nullptr;
-  W* no_next_degree = nullptr;
-  hipLaunchKernelGGL((hub_final_kernel<W, BLOCK, true>),
-                     dim3((nhub + WAVES - 1) / WAVES), dim3(BLOCK), 0, stream,
-                     hubs, nhub, hub_self, p_wcc, curr_comm, v_degree,
-                     no_size, comm_degree, comm_gid, gid_base, n_local,
-                     constant, p_gain, p_gid, p_dense, r_key, r_sum,
-                     target_hub, cw_hub, no_next_size, no_next_degree,
-                     (int64_t)0, mover_bound, cand_bound);
+void launch_hub_argmax(const HubArgs<W>& args, hipStream_t stream) {
+  if (args.nhub == 0) return;
+  if (args.mover_bound != nullptr)
+    launch_hub_argmax_impl<W, true>(args, stream);
+  else
+    launch_hub_argmax_impl<W, false>(args, stream);
 }
-#define INSTANTIATE_HUB_REFINE(W)                                             \
-  template void launch_hub_refine_argmax<W>(                                  \
-      const int32_t*, const W*, const int64_t*, const int32_t*, int,          \
-      const double*, const int32_t*, const W*, const W*, const int64_t*,      \
-      int64_t, int32_t, double, double*, double*, int64_t*, int32_t*,         \
-      int32_t*, double*, int32_t*, W*, const int32_t*, const int32_t*,        \
-      hipStream_t);
-INSTANTIATE_HUB_REFINE(float)
-INSTANTIATE_HUB_REFINE(double)
+template void launch_hub_argmax<float>(const HubArgs<float>&, hipStream_t);
+template void launch_hub_argmax<double>(const HubArgs<double>&, hipStream_t);
 
 int hub_slices() { return HUB_SLICES; }
 

@@ -23,6 +23,7 @@ setup(
                 "cuvite_amd/ops/csrc/bindings.cpp",
                 "cuvite_amd/ops/csrc/louvain_kernels.hip",
             ],
+            depends=["cuvite_amd/ops/csrc/launch.h"],
             extra_compile_args={
                 "cxx": ["-O3", "-std=c++17"],
                 "nvcc": ["-O3", "-std=c++17"],
