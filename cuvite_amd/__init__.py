@@ -17,6 +17,9 @@ from .quality import (PartitionQuality, intra_weight_torch,
 from .connectivity import (ConnectivityReport, cc_components_torch,
                            split_disconnected)
 from .refine import RefineReport, refine_coin, refine_partition
+from .dynamic import (EdgeBatch, FrontierReport, affected_vertices,
+                      apply_edge_batch, frontier_expand_torch,
+                      frontier_move_torch, run_frontier_phase)
 
 __all__ = [
     "Graph",
@@ -34,5 +37,12 @@ __all__ = [
     "RefineReport",
     "refine_coin",
     "refine_partition",
+    "EdgeBatch",
+    "FrontierReport",
+    "apply_edge_batch",
+    "affected_vertices",
+    "run_frontier_phase",
+    "frontier_move_torch",
+    "frontier_expand_torch",
     "__version__",
 ]

@@ -115,6 +115,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--init-communities", metavar="FILE", default="",
                     help="warm start: begin clustering from the partition "
                     "in FILE instead of singletons (-z applies)")
+    ap.add_argument("--update-edges", metavar="FILE", default="",
+                    help="dynamic update: the graph given by -f or a "
+                    "generator is the OLD graph, --init-communities its "
+                    "partition; FILE holds the edge changes, one per line, "
+                    "'a u v [w]' to add and 'd u v' to delete (0-based ids, "
+                    "# comments). Phase 0 then sweeps only the affected "
+                    "vertices and what their moves reach")
     ap.add_argument("--exact-modularity", action="store_true",
                     help="after the run, print the exact modularity of the "
                     "returned partition (\"Final modularity\" is the "
@@ -151,6 +158,16 @@ def validate(args, world: int):
         sys.exit("Cannot enable both -p and -i")
     if args.leiden and args.connectivity == "level":
         sys.exit("Cannot enable both --leiden and --connectivity level")
+    if args.update_edges:
+        if not args.init_communities:
+            sys.exit("--update-edges needs --init-communities")
+        if args.score_communities:
+            sys.exit("--update-edges does not combine with "
+                     "--score-communities")
+        if (args.coloring or args.ordering or args.early_term
+                or args.threshold_cycling):
+            sys.exit("--update-edges cannot be combined with -c, -d, -t "
+                     "or -i")
     if args.early_term and not 1 <= args.early_term <= 4:
         sys.exit("-t must be 1..4")
     if args.early_term in (2, 4) and not 0.0 <= args.et_alpha <= 1.0:
@@ -220,6 +237,44 @@ def _load_partition_slice(path: str, args, dg: DistGraph) -> torch.Tensor:
     _, inv = np.unique(lab.numpy(), return_inverse=True)
     inv = torch.from_numpy(inv.astype(np.int64).reshape(-1))
     return inv[dg.base:dg.bound].to(dg.g.device)
+
+
+def _load_edge_batch(path: str, nv_global: int):
+    """The edge batch in `path`: lines 'a u v [w]' (add, weight 1 if absent)
+    and 'd u v' (delete), 0-based ids, '#' starts a comment. Every rank reads
+    the whole file, so every rank takes the same exit on a bad one."""
+    from .dynamic import EdgeBatch
+    ins, dels = [], []
+    try:
+        with open(path) as f:
+            lines = f.readlines()
+    except FileNotFoundError:
+        sys.exit(f"Error opening edge update file: {path}")
+    for no, line in enumerate(lines, 1):
+        tok = line.split("#", 1)[0].split()
+        if not tok:
+            continue
+        try:
+            if tok[0] == "a" and len(tok) in (3, 4):
+                ins.append((int(tok[1]), int(tok[2]),
+                            float(tok[3]) if len(tok) == 4 else 1.0))
+            elif tok[0] == "d" and len(tok) == 3:
+                dels.append((int(tok[1]), int(tok[2])))
+            else:
+                raise ValueError
+            u, v = int(tok[1]), int(tok[2])
+            if not (0 <= u < nv_global and 0 <= v < nv_global):
+                raise ValueError
+        except ValueError:
+            sys.exit(f"{path}:{no}: expected 'a u v [w]' or 'd u v' with "
+                     f"vertex ids in [0, {nv_global})")
+    i64 = torch.int64
+    return EdgeBatch(
+        torch.tensor([e[0] for e in ins], dtype=i64),
+        torch.tensor([e[1] for e in ins], dtype=i64),
+        torch.tensor([e[2] for e in ins], dtype=torch.float64),
+        torch.tensor([e[0] for e in dels], dtype=i64),
+        torch.tensor([e[1] for e in dels], dtype=i64))
 
 
 def _print_connectivity(dg: DistGraph, labels: torch.Tensor, comm: Comm,
@@ -294,6 +349,23 @@ def main(argv=None) -> int:
     init_labels = None
     if args.init_communities:
         init_labels = _load_partition_slice(args.init_communities, args, dg)
+    init_frontier = None
+    if args.update_edges:
+        # the ingested graph is the old one; rank 0 passes the whole batch,
+        # the other ranks an empty share
+        from .dynamic import EdgeBatch, affected_vertices, apply_edge_batch
+        batch = _load_edge_batch(args.update_edges, dg.nv_global)
+        n_ins, n_del = batch.ins_src.numel(), batch.del_src.numel()
+        share = batch if comm.rank == 0 else EdgeBatch.empty()
+        try:
+            dg = apply_edge_batch(dg, comm, share)
+        except ValueError as e:
+            sys.exit(f"{args.update_edges}: {e}")
+        init_frontier = affected_vertices(dg, comm, init_labels, share)
+        n_aff = int(comm.allreduce_scalar(float(init_frontier.sum())))
+        if comm.rank == 0:
+            print(f"Edge batch: inserted={n_ins} deleted={n_del} "
+                  f"affected={n_aff}")
 
     vo_inv = None     # new local pos -> old local pos (inverse applied later)
     vo_gmap = None    # old gid -> new gid
@@ -326,6 +398,8 @@ def main(argv=None) -> int:
             # relabelled local position p holds input-order vertex
             # vo_order[p]; community ids are opaque, so values stay
             init_labels = init_labels[vo_order]
+            if init_frontier is not None:
+                init_frontier = init_frontier[vo_order]
         pq = partition_quality(dg, init_labels, comm, backend=args.backend)
         if comm.rank == 0:
             print(f"Initial partition: modularity={pq.modularity:.15g} "
@@ -333,11 +407,17 @@ def main(argv=None) -> int:
 
     comm.barrier()
     t0 = time.perf_counter()
-    res = louvain(dg, comm, cfg, init_labels=init_labels)
+    res = louvain(dg, comm, cfg, init_labels=init_labels,
+                  init_frontier=init_frontier)
     comm.barrier()
     t_total = time.perf_counter() - t0
 
     if comm.rank == 0:
+        fr = res.levels[0].get("frontier") if res.levels else None
+        if fr is not None:
+            # against what as many full sweeps would have evaluated
+            print(f"Frontier phase: sweeps={fr.sweeps} "
+                  f"evaluated={fr.evaluated} of {fr.sweeps * dg.nv_global}")
         for lvl, q in enumerate(res.modularity_per_level):
             print(f"Level {lvl}: modularity = {q:.6f}")
         for lvl, entry in enumerate(res.levels):

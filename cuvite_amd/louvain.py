@@ -336,14 +336,18 @@ class PhaseState:
         comm_gid = torch.cat([self._local_gids(), self._runiv])
         return self._dense, self._runiv, comm_size, comm_degree, comm_gid
 
-    def apply_moves(self, target_gid: torch.Tensor, remote_gids: torch.Tensor):
+    def apply_moves(self, target_gid: torch.Tensor, remote_gids: torch.Tensor,
+                    recount: bool = True):
         """Apply community size/degree deltas for vertices that moved
-        (ref 4-case update, louvain.cpp:2308-2376 + updateRemoteCommunities)."""
+        (ref 4-case update, louvain.cpp:2308-2376 + updateRemoteCommunities).
+        `recount=False` keeps a single HIP rank on the delta kernel as well:
+        a frontier sweep moves few vertices, and a recount of all of them
+        into a warm start's few communities serialises on their counters."""
         dg = self.dg
         base, bound = dg.base, dg.bound
         if getattr(self, "use_hip", False) and target_gid.is_cuda:
             from . import ops
-            if self.comm.world == 1:
+            if self.comm.world == 1 and recount:
                 # fresh recount beats the delta update when most vertices
                 # move (2 atomics/vertex vs 4 per moved vertex; rocprof
                 # 25 -> ~12 ms at s26's oscillating sweeps)
@@ -354,6 +358,8 @@ class PhaseState:
             ops.apply_deltas_(target_gid, self.curr_comm, self.v_degree,
                               base, bound, self.local_size,
                               self.local_degree)
+            if self.comm.world == 1:
+                return
             moved = target_gid != self.curr_comm
             src = self.curr_comm[moved]
             dst = target_gid[moved]
@@ -660,7 +666,8 @@ def _refined_init_labels(level: DistGraph, comm: Comm, cvect: torch.Tensor,
 def louvain(dg: DistGraph, comm: Optional[Comm] = None,
             cfg: Optional[LouvainConfig] = None,
             halo=None,
-            init_labels: Optional[torch.Tensor] = None) -> LouvainResult:
+            init_labels: Optional[torch.Tensor] = None,
+            init_frontier: Optional[torch.Tensor] = None) -> LouvainResult:
     """Full multi-phase Louvain (ref main.cpp:218-495). Returns the final
     community id per ORIGINAL local vertex (contiguous global ids) and the
     final modularity. `halo`: optional prebuilt HaloContext for the INPUT
@@ -668,7 +675,14 @@ def louvain(dg: DistGraph, comm: Optional[Comm] = None,
     region) pass it to avoid a duplicate ghost structure (17 GB at s27).
     `init_labels`: warm start — int64 [nv] global community ids in
     [0, nv_global) for this rank's vertices; phase 0 starts from them
-    instead of singletons (ValueError on every rank if any slice is bad)."""
+    instead of singletons (ValueError on every rank if any slice is bad).
+    `init_frontier`: with init_labels, a bool mask over this rank's vertices;
+    phase 0 becomes the dynamic-frontier phase (dynamic.run_frontier_phase):
+    its first sweep evaluates the marked vertices only and every later one
+    the moved vertices and their neighbours. levels[0]["frontier"] carries
+    the FrontierReport. Coloring, ordering, early termination and threshold
+    scaling cannot be combined with it; one_phase, connectivity and
+    algorithm="leiden" act after the phase and compose unchanged."""
     from .coarsen import coarsen, remap_labels
     from .coloring import distance1_coloring
 
@@ -679,6 +693,14 @@ def louvain(dg: DistGraph, comm: Optional[Comm] = None,
         raise ValueError(f"unknown connectivity mode {cfg.connectivity!r}")
     if cfg.algorithm not in ("louvain", "leiden"):
         raise ValueError(f"unknown algorithm {cfg.algorithm!r}")
+    if init_frontier is not None:
+        if init_labels is None:
+            raise ValueError("init_frontier needs init_labels")
+        for flag in ("coloring", "ordering", "early_term",
+                     "threshold_scaling"):
+            if getattr(cfg, flag):
+                raise ValueError(f"init_frontier cannot be combined with "
+                                 f"{flag}")
     leiden = cfg.algorithm == "leiden"
     if leiden and cfg.connectivity == "level":
         raise ValueError("algorithm='leiden' refines every level itself; "
@@ -731,10 +753,18 @@ def louvain(dg: DistGraph, comm: Optional[Comm] = None,
             if comm.world > 1 else float(level.ne)
         t0 = time.perf_counter()
         halo = None  # phase-0 halo ownership moves to run_phase/coarsen
-        curr_mod, cvect, iters, phase_halo = run_phase(
-            level, comm, cfg, curr_mod, threshold,
-            colors=colors, num_colors=num_colors, halo=pre_halo,
-            init_labels=init_labels if phase == 0 else next_init)
+        frontier_report = None
+        if phase == 0 and init_frontier is not None:
+            from .dynamic import run_frontier_phase
+            curr_mod, cvect, iters, phase_halo, frontier_report = \
+                run_frontier_phase(level, comm, cfg, init_labels,
+                                   init_frontier, halo=pre_halo,
+                                   lower=curr_mod, threshold=threshold)
+        else:
+            curr_mod, cvect, iters, phase_halo = run_phase(
+                level, comm, cfg, curr_mod, threshold,
+                colors=colors, num_colors=num_colors, halo=pre_halo,
+                init_labels=init_labels if phase == 0 else next_init)
         pre_halo = None
         t_cluster = time.perf_counter() - t0
         times["clustering"] += t_cluster
@@ -742,6 +772,8 @@ def louvain(dg: DistGraph, comm: Optional[Comm] = None,
         level_entry = {"ne_global": ne_global, "iters": iters,
                        "modularity": curr_mod, "cluster_s": t_cluster,
                        "rebuild_s": 0.0}
+        if frontier_report is not None:
+            level_entry["frontier"] = frontier_report
         levels.append(level_entry)
 
         if (curr_mod - prev_mod) > threshold:

@@ -80,6 +80,32 @@ def _buckets_for(rowptr: torch.Tensor):
     return vlists, hubs64, hdeg
 
 
+_class_id_cache: dict = {}
+FRONTIER_HUB_CLASS = 7        # class ids of frontier_lists beyond the seven
+FRONTIER_EDGELESS_CLASS = 8   # LDS classes
+
+
+def _class_ids_for(rowptr: torch.Tensor) -> torch.Tensor:
+    """uint8 [nv] degree class of every vertex (static per phase; cached like
+    _bucket_cache): 0-6 the LDS classes of _CLASS_BOUNDS and the hub cut, 7
+    hubs, 8 vertices without edges."""
+    cut = _hub_cut()
+    key = (rowptr.data_ptr(), rowptr.numel(), cut)
+    hit = _class_id_cache.get(key)
+    if hit is not None and hit[0] is rowptr:
+        return hit[1]
+    deg = rowptr[1:] - rowptr[:-1]
+    bounds = torch.tensor(_CLASS_BOUNDS + (cut,), dtype=torch.int64,
+                          device=rowptr.device)
+    # bucketize: class c holds bounds[c - 1] < deg <= bounds[c]
+    cls = torch.bucketize(deg, bounds).to(torch.uint8)
+    cls[deg == 0] = FRONTIER_EDGELESS_CLASS
+    if len(_class_id_cache) > 8:
+        _class_id_cache.clear()
+    _class_id_cache[key] = (rowptr, cls)
+    return cls
+
+
 _side_streams: dict = {}
 
 
@@ -88,6 +114,7 @@ def clear_phase_caches():
     hub chunk groups). Called by the phase loop before coarsening: at s27
     the cached hub arrays are tens of GB and the next level re-keys anyway."""
     _bucket_cache.clear()
+    _class_id_cache.clear()
     _hub_static_cache.clear()
     _hub_groups_cache.clear()
 
@@ -361,12 +388,21 @@ def _class_streams_enabled() -> bool:
     return os.environ.get("CUVITE_CLASS_STREAMS", "1") not in ("0", "off")
 
 
-def _classes_beside_hubs(dev, hubs64, run_hub_sort, classes, hub_moves):
-    """Shared tail of local_move and refine_move. `classes()` launches the
-    degree-class kernels and returns (target [nv], cw [nv]); `hub_moves()`
-    runs the hub pipeline and returns the per-hub pair aligned with hubs64,
-    which is scattered into the class result. With `run_hub_sort` false only
-    the classes run."""
+def _classes_beside_hubs(dev, hubs64, run_hub_sort, classes, hub_moves,
+                         hub_mask=None):
+    """Shared tail of local_move, refine_move and frontier_move. `classes()`
+    launches the degree-class kernels and returns (target [nv], cw [nv]);
+    `hub_moves()` runs the hub pipeline and returns the per-hub pair aligned
+    with hubs64, which is scattered into the class result. With
+    `run_hub_sort` false only the classes run. `hub_mask` (bool, aligned
+    with hubs64): scatter only those hubs' results."""
+    if hub_mask is not None and run_hub_sort:
+        inner = hub_moves
+        hubs64 = hubs64[hub_mask]
+
+        def hub_moves():
+            t, w = inner()
+            return t[hub_mask], w[hub_mask]
     if run_hub_sort and not os.environ.get("CUVITE_NO_OVERLAP"):
         # disjoint vertex sets: run the HIP class kernels on a side stream
         # concurrently with the (longer) hub pipeline on the main stream;
@@ -507,6 +543,96 @@ def refine_move(inp, mover_bound: torch.Tensor, cand_bound: torch.Tensor,
     return _classes_beside_hubs(
         dev, hubs64, run_hub_sort, classes,
         lambda: _hub_moves_sorted(inp, hubs64, hdeg, None, bounds))
+
+
+def _as_u8(active: torch.Tensor) -> torch.Tensor:
+    """A bool or uint8 mask as uint8 over the same storage."""
+    if active.dtype == torch.bool:
+        return active.view(torch.uint8)
+    if active.dtype != torch.uint8:
+        raise TypeError("active must be a bool or uint8 mask")
+    return active
+
+
+def frontier_span() -> int:
+    """Edges per wave span of the frontier_expand kernel (tests build their
+    shapes around it)."""
+    return int(_require().frontier_span())
+
+
+def frontier_expand(changed: torch.Tensor, rowptr: torch.Tensor,
+                    tails_dense: torch.Tensor, g_rowptr: torch.Tensor,
+                    g_heads: torch.Tensor, active: torch.Tensor) -> torch.Tensor:
+    """active[u] = 1 for every changed local id and for every local
+    neighbour u of a changed dense id, in place (twin:
+    dynamic.frontier_expand_torch). `changed`: int32 dense ids in
+    [0, nv + ng), locals and ghosts in any order; `rowptr` / `tails_dense`:
+    the level CSR; `g_rowptr` int64 [ng + 1] / `g_heads` int32: the ghost ->
+    local reverse adjacency (dynamic.ghost_reverse_csr); `active`: bool or
+    uint8 [nv]. Work is proportional to the summed degree of the changed
+    rows; no host sync. Returns `active`."""
+    _require().frontier_expand(changed, rowptr, tails_dense, g_rowptr,
+                               g_heads, _as_u8(active))
+    return active
+
+
+def frontier_lists(rowptr: torch.Tensor, active: torch.Tensor):
+    """Per-class vertex lists of the active vertices, built on the device in
+    one compaction with ONE host sync (the copy of the nine counts). Returns
+    nine ascending int32 lists: the seven LDS degree classes (what
+    local_move_bucketed takes), the active hubs (FRONTIER_HUB_CLASS) and the
+    active vertices without edges (FRONTIER_EDGELESS_CLASS). The lists are
+    views of one buffer."""
+    cls = _class_ids_for(rowptr)
+    lists, counts = _require().frontier_compact(_as_u8(active), cls)
+    out, lo = [], 0
+    for n in counts.tolist():  # the sweep's host sync
+        out.append(lists[lo:lo + n])
+        lo += n
+    return out
+
+
+def frontier_move(inp, active: torch.Tensor, cw_prev: torch.Tensor,
+                  lists=None):
+    """HIP local move over the vertices marked in `active` (bool or uint8
+    [nv]) only; twin: dynamic.frontier_move_torch. Returns (target dense comm
+    ids [nv], cluster_weight [nv]): an active vertex gets exactly what
+    local_move gives it, an inactive one keeps its label and its entry of
+    `cw_prev` (weight dtype [nv], not modified). `lists`: the result of
+    frontier_lists(inp.rowptr, active) if the caller already has it.
+
+    The degree-class kernels run over the compacted class lists as they are.
+    Hubs: the pipeline is skipped when no hub is active; otherwise it runs
+    over the phase's cached full hub list (the flattened hub adjacency is
+    keyed by that list) and only the active hubs' results are scattered."""
+    ext = _require()
+    if lists is None:
+        lists = frontier_lists(inp.rowptr, active)
+    vlists = list(lists[:7])
+    act_hubs = lists[FRONTIER_HUB_CLASS]
+    edgeless = lists[FRONTIER_EDGELESS_CLASS]
+    nv = inp.nv
+    dev = inp.rowptr.device
+    target = torch.empty(nv, dtype=torch.int32, device=dev)
+    cw = cw_prev.to(inp.weights.dtype).clone().contiguous()
+    if edgeless.numel():
+        cw[edgeless.to(torch.int64)] = 0  # what the move gives an edgeless row
+    kw = dict(_gid_args(inp), class_streams=_class_streams_enabled(),
+              out_target=target, out_cw=cw, keep_cw=True)
+
+    def classes():
+        return ext.local_move_bucketed(
+            inp.rowptr, inp.tails, inp.weights, inp.curr_comm, inp.v_degree,
+            inp.comm_size, inp.comm_degree, inp.comm_gid, float(inp.constant),
+            vlists, **kw)
+
+    if act_hubs.numel() == 0:
+        return _classes_beside_hubs(dev, None, False, classes, None)
+    _, hubs64, hdeg = _buckets_for(inp.rowptr)
+    hub_mask = active[hubs64].to(torch.bool)
+    return _classes_beside_hubs(
+        dev, hubs64, True, classes,
+        lambda: _hub_moves_sorted(inp, hubs64, hdeg), hub_mask=hub_mask)
 
 
 def modularity_parts(cluster_weight: torch.Tensor,

@@ -140,7 +140,7 @@ std::vector<at::Tensor> local_move_impl(
     c10::optional<at::Tensor> next_degree, bool class_streams,
     const int32_t* mover_bound, const int32_t* cand_bound,
     c10::optional<at::Tensor> out_target = c10::nullopt,
-    c10::optional<at::Tensor> out_cw = c10::nullopt) {
+    c10::optional<at::Tensor> out_cw = c10::nullopt, bool keep_cw = false) {
   CHECK_INPUT(rowptr);
   CHECK_INPUT(tails);
   CHECK_INPUT(weights);
@@ -168,8 +168,10 @@ std::vector<at::Tensor> local_move_impl(
     target = *out_target;
     cw = *out_cw;
     target.copy_(curr_comm.narrow(0, 0, nv));
-    cw.zero_();
+    // keep_cw: a vertex in no list keeps the caller's value (frontier sweep)
+    if (!keep_cw) cw.zero_();
   } else {
+    TORCH_CHECK(!keep_cw, "keep_cw needs out_cw");
     target = curr_comm.narrow(0, 0, nv).clone();
     cw = at::zeros({nv}, weights.options());
   }
@@ -217,11 +219,14 @@ std::vector<at::Tensor> local_move(
     at::Tensor comm_degree, at::Tensor comm_gid, double constant,
     std::vector<at::Tensor> vlists, int64_t gid_base, int64_t n_local,
     c10::optional<at::Tensor> next_size,
-    c10::optional<at::Tensor> next_degree, bool class_streams) {
+    c10::optional<at::Tensor> next_degree, bool class_streams,
+    c10::optional<at::Tensor> out_target, c10::optional<at::Tensor> out_cw,
+    bool keep_cw) {
   return local_move_impl(rowptr, tails, weights, curr_comm, v_degree,
                          comm_size, comm_degree, comm_gid, constant, vlists,
                          gid_base, n_local, next_size, next_degree,
-                         class_streams, nullptr, nullptr);
+                         class_streams, nullptr, nullptr, out_target, out_cw,
+                         keep_cw);
 }
 
 // The two bound arrays of a refine round: mover_bound int32 [>= nv] (bound
@@ -669,6 +674,98 @@ std::tuple<at::Tensor, int64_t> cc_components(at::Tensor rowptr,
   return {comp, rounds};
 }
 
+// Frontier expansion (see frontier_expand_kernel): active[u] = 1 for every
+// changed local id and every local neighbour u of a changed dense id.
+// changed: int32 [nc] dense ids in [0, nv + ng); rowptr / tails: the level
+// CSR with dense tails; g_rowptr / g_heads: ghost -> local reverse CSR
+// (g_rowptr int64 [ng + 1]); active: uint8 [nv], written in place. No host
+// sync: the prefix sums over the changed rows' degrees stay on the device.
+void frontier_expand(at::Tensor changed, at::Tensor rowptr, at::Tensor tails,
+                     at::Tensor g_rowptr, at::Tensor g_heads,
+                     at::Tensor active) {
+  CHECK_INPUT(changed);
+  CHECK_INPUT(rowptr);
+  CHECK_INPUT(tails);
+  CHECK_INPUT(g_rowptr);
+  CHECK_INPUT(g_heads);
+  CHECK_INPUT(active);
+  TORCH_CHECK(changed.scalar_type() == at::kInt, "changed must be int32");
+  TORCH_CHECK(rowptr.scalar_type() == at::kLong &&
+              g_rowptr.scalar_type() == at::kLong,
+              "rowptr / g_rowptr must be int64");
+  TORCH_CHECK(tails.scalar_type() == at::kInt &&
+              g_heads.scalar_type() == at::kInt,
+              "tails / g_heads must be int32");
+  TORCH_CHECK(active.scalar_type() == at::kByte, "active must be uint8");
+  TORCH_CHECK(rowptr.numel() >= 1 && g_rowptr.numel() >= 1,
+              "rowptr / g_rowptr must have n + 1 entries");
+  const int64_t nv = rowptr.numel() - 1;
+  const int64_t ng = g_rowptr.numel() - 1;
+  TORCH_CHECK(active.numel() == nv, "active must have one entry per vertex");
+  TORCH_CHECK(nv + ng < (int64_t)INT32_MAX,
+              "nv + ng exceeds the int32 dense id range");
+  const int64_t nc = changed.numel();
+  if (nc == 0 || nv == 0) return;
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  cuvite::FrontierArgs a{};
+  a.changed = changed.data_ptr<int32_t>();
+  a.nc = nc;
+  a.rowptr = rowptr.data_ptr<int64_t>();
+  a.tails = tails.data_ptr<int32_t>();
+  a.nv = nv;
+  a.ne = tails.numel();
+  a.g_rowptr = g_rowptr.data_ptr<int64_t>();
+  a.g_heads = g_heads.data_ptr<int32_t>();
+  a.ng = ng;
+  a.neg = g_heads.numel();
+  a.active = active.data_ptr<uint8_t>();
+  auto offs = at::zeros({nc + 1}, rowptr.options());
+  auto deg = at::empty({nc}, rowptr.options());
+  cuvite::launch_frontier_degrees(a, deg.data_ptr<int64_t>(), stream);
+  offs.narrow(0, 1, nc).copy_(at::cumsum(deg, 0));
+  // a row is at most as long as its CSR, so this bounds offs[nc] for a
+  // duplicate-free list; a longer total is covered by the span stride
+  const int64_t edge_bound = a.ne + a.neg;
+  cuvite::launch_frontier_expand(a, offs.data_ptr<int64_t>(), edge_bound,
+                                 stream);
+  C10_HIP_CHECK(hipGetLastError());
+}
+
+// Class lists of the active vertices (see frontier_compact_kernel). active:
+// uint8 [nv]; cls: uint8 [nv], class id per vertex in [0, frontier_classes()).
+// Returns (lists int32 [nv], counts int32 [frontier_classes()]): class c's
+// ascending vertex ids sit at lists[sum(counts[:c]) : sum(counts[:c + 1])].
+// Both stay on the device; the caller reads counts with one copy.
+std::vector<at::Tensor> frontier_compact(at::Tensor active, at::Tensor cls) {
+  CHECK_INPUT(active);
+  CHECK_INPUT(cls);
+  TORCH_CHECK(active.scalar_type() == at::kByte &&
+              cls.scalar_type() == at::kByte, "active / cls must be uint8");
+  const int64_t nv = active.numel();
+  TORCH_CHECK(cls.numel() == nv, "active / cls length mismatch");
+  TORCH_CHECK(nv < (int64_t)INT32_MAX, "nv exceeds the int32 dense id range");
+  const int C = cuvite::frontier_classes();
+  auto i32 = active.options().dtype(at::kInt);
+  auto lists = at::empty({nv}, i32);
+  if (nv == 0) return {lists, at::zeros({C}, i32)};
+  const int64_t nunit = cuvite::frontier_units(nv);
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  auto unit_cnt = at::empty({nunit, C}, i32);
+  cuvite::launch_frontier_compact(
+      active.data_ptr<uint8_t>(), cls.data_ptr<uint8_t>(), nv,
+      unit_cnt.data_ptr<int32_t>(), nullptr, nullptr, nullptr, false, stream);
+  auto incl = at::cumsum(unit_cnt, 0, at::kInt);
+  auto counts = incl.select(0, nunit - 1).contiguous();
+  auto unit_off = (incl - unit_cnt).contiguous();
+  auto class_base = (at::cumsum(counts, 0, at::kInt) - counts).contiguous();
+  cuvite::launch_frontier_compact(
+      active.data_ptr<uint8_t>(), cls.data_ptr<uint8_t>(), nv, nullptr,
+      unit_off.data_ptr<int32_t>(), class_base.data_ptr<int32_t>(),
+      lists.data_ptr<int32_t>(), true, stream);
+  C10_HIP_CHECK(hipGetLastError());
+  return {lists, counts};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -679,7 +776,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("comm_degree"), py::arg("comm_gid"), py::arg("constant"),
         py::arg("vlists"), py::arg("gid_base") = 0, py::arg("n_local") = 0,
         py::arg("next_size") = py::none(),
-        py::arg("next_degree") = py::none(), py::arg("class_streams") = true);
+        py::arg("next_degree") = py::none(), py::arg("class_streams") = true,
+        py::arg("out_target") = py::none(), py::arg("out_cw") = py::none(),
+        py::arg("keep_cw") = false);
   m.def("refine_move_bucketed", &refine_move,
         "Leiden refine round (HIP, degree-class routed, bound-filtered)",
         py::arg("rowptr"), py::arg("tails"), py::arg("weights"),
@@ -720,6 +819,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cc_components", &cc_components,
         "connected components over same-label edges, hook + compress rounds "
         "(HIP); returns (comp, rounds)");
+  m.def("frontier_expand", &frontier_expand,
+        "mark the changed locals and the local neighbours of the changed "
+        "dense ids, span-balanced (HIP)",
+        py::arg("changed"), py::arg("rowptr"), py::arg("tails"),
+        py::arg("g_rowptr"), py::arg("g_heads"), py::arg("active"));
+  m.def("frontier_span", &cuvite::frontier_span,
+        "edges per wave span of the frontier_expand kernel");
+  m.def("frontier_compact", &frontier_compact,
+        "ascending per-class lists of the active vertices and their counts "
+        "(HIP); returns (lists, counts)",
+        py::arg("active"), py::arg("cls"));
+  m.def("frontier_classes", &cuvite::frontier_classes,
+        "number of class ids frontier_compact sorts into");
   m.def("hub_slices", &cuvite::hub_slices,
         "element slices per hub segment in the hub argmax kernels");
   m.def("hub_moves", &hub_moves,

@@ -134,6 +134,40 @@ void launch_cc_hook(const int64_t* rowptr, const int32_t* tails,
                     int32_t* comp, int32_t* changed, hipStream_t stream);
 void launch_cc_compress(int32_t* comp, int64_t nl, hipStream_t stream);
 
+// Arguments of the frontier expansion (frontier_degrees_kernel,
+// frontier_expand_kernel): the changed dense ids and the two CSRs their
+// neighbours are read from.
+struct FrontierArgs {
+  const int32_t* changed;   // int32 [nc]: dense ids in [0, nv + ng)
+  int64_t nc;
+  const int64_t* rowptr;    // int64 [nv + 1]: level CSR, local rows
+  const int32_t* tails;     // int32 [ne]: dense tails (ghosts >= nv skipped)
+  int64_t nv, ne;
+  const int64_t* g_rowptr;  // int64 [ng + 1]: ghost -> local reverse CSR
+  const int32_t* g_heads;   // int32 [neg]: local heads of each ghost
+  int64_t ng, neg;
+  uint8_t* active;          // out uint8 [nv]: 1 is stored, nothing cleared
+};
+
+void launch_frontier_degrees(const FrontierArgs& args, int64_t* deg_out,
+                             hipStream_t stream);
+// offs: int64 [nc + 1], exclusive prefix sums of deg_out; edge_bound: any
+// host-side upper estimate of offs[nc] (sizes the grid only).
+void launch_frontier_expand(const FrontierArgs& args, const int64_t* offs,
+                            int64_t edge_bound, hipStream_t stream);
+int frontier_span();
+// Class lists of the active vertices. cls: uint8 [nv] class id per vertex in
+// [0, frontier_classes()). write == false: per-wave class counts into
+// unit_cnt [frontier_units(nv) * frontier_classes()]. write == true: ids into
+// lists [nv] at class_base[c] + unit_off[unit][c] + rank, ascending.
+void launch_frontier_compact(const uint8_t* active, const uint8_t* cls,
+                             int64_t nv, int32_t* unit_cnt,
+                             const int32_t* unit_off,
+                             const int32_t* class_base, int32_t* lists,
+                             bool write, hipStream_t stream);
+int frontier_classes();
+int64_t frontier_units(int64_t nv);
+
 // rocPRIM wrappers, two-phase: temp == nullptr only stores the scratch size
 // in *bytes, a second call with that much scratch at temp does the work.
 template <typename W>

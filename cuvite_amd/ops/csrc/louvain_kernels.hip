@@ -940,6 +940,145 @@ __global__ void cc_compress_kernel(int32_t* comp, int64_t nl) {
 }
 
 // ---------------------------------------------------------------------------
+// Frontier sweeps (cuvite_amd/dynamic.py): a sweep evaluates only the
+// vertices marked in a byte mask `active` [nv]. Two steps build that sweep's
+// inputs on the device.
+//
+// Expand: given the dense ids whose label changed (locals in [0, nv), ghosts
+// in [nv, nv + ng)), mark the changed locals and every local neighbour of a
+// changed id. Neighbours of a local row come from the level CSR, those of a
+// ghost from a ghost -> local reverse CSR. frontier_degrees_kernel stores the
+// degree of every changed row (and marks the changed locals); the host side
+// turns the degrees into the prefix array `offs`, which concatenates the
+// changed rows into one edge space of offs[nc] edges. frontier_expand_kernel
+// cuts that space into spans of FX_SPAN edges, one wave each, exactly as
+// intra_weight_kernel cuts the whole edge list: first row of the span by a
+// binary search in offs, last row by a gallop (span_row_range), each lane's
+// row by a search inside that range. Work is proportional to the summed
+// degree of the changed rows and a changed hub is spread over many waves.
+// Marks are plain byte stores of 1: idempotent, so neither order nor
+// duplicates matter and there are no atomics. Every loop is bounded by the
+// span. An id outside [0, nv + ng) has degree 0; a neighbour outside [0, nv)
+// (a ghost tail in a local row) is skipped.
+//
+// Compact: from `active` and the phase-static degree class of every vertex
+// (0-6 the LDS classes, 7 hub, 8 edgeless) produce the ascending vertex list
+// of every class in one buffer. A wave owns FC_UNIT consecutive vertices and
+// ranks its members per class with ballots, so the lists are stable. Pass 1
+// (WRITE = false) stores the per-wave class counts; the host side scans them
+// into per-wave offsets and class bases with no sync; pass 2 (WRITE = true)
+// repeats the ballots and stores the ids. No atomics.
+// ---------------------------------------------------------------------------
+
+constexpr int FX_SPAN = 1024;   // edges per wave in frontier_expand_kernel
+constexpr int FC_CLASSES = 9;   // 7 LDS classes, hubs, edgeless
+constexpr int FC_ITEMS = 16;    // 64-vertex chunks per wave
+constexpr int FC_UNIT = 64 * FC_ITEMS;
+
+// Degree of dense id x: a local row, a ghost row, or nothing.
+DEV_INLINE int64_t fx_degree(const int64_t* __restrict__ rowptr, int64_t nv,
+                             const int64_t* __restrict__ g_rowptr, int64_t ng,
+                             int32_t x) {
+  if (x < 0) return 0;
+  if (x < nv) return rowptr[x + 1] - rowptr[x];
+  const int64_t g = (int64_t)x - nv;
+  return g < ng ? g_rowptr[g + 1] - g_rowptr[g] : 0;
+}
+
+__global__ void frontier_degrees_kernel(
+    const int32_t* __restrict__ changed, int64_t nc,
+    const int64_t* __restrict__ rowptr, int64_t nv,
+    const int64_t* __restrict__ g_rowptr, int64_t ng,
+    int64_t* __restrict__ deg_out, uint8_t* __restrict__ active) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nc;
+       i += stride) {
+    const int32_t x = changed[i];
+    deg_out[i] = fx_degree(rowptr, nv, g_rowptr, ng, x);
+    if (x >= 0 && x < nv) active[x] = 1;
+  }
+}
+
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void frontier_expand_kernel(
+    const int32_t* __restrict__ changed, int64_t nc,
+    const int64_t* __restrict__ offs, const int64_t* __restrict__ rowptr,
+    const int32_t* __restrict__ tails, int64_t nv, int64_t ne,
+    const int64_t* __restrict__ g_rowptr, const int32_t* __restrict__ g_heads,
+    int64_t ng, int64_t neg, uint8_t* __restrict__ active) {
+  constexpr int WAVES = BLOCK / 64;
+  const int lane = threadIdx.x % 64;
+  const int64_t total = offs[nc];
+  const int64_t nspan = (total + FX_SPAN - 1) / FX_SPAN;
+  const int64_t sstride = (int64_t)gridDim.x * WAVES;
+  for (int64_t s = (int64_t)blockIdx.x * WAVES + threadIdx.x / 64; s < nspan;
+       s += sstride) {
+    const int64_t s0 = s * FX_SPAN;
+    const int64_t s1 = (s0 + FX_SPAN < total) ? s0 + FX_SPAN : total;
+    int64_t rlo, rhi;
+    span_row_range(offs, nc, s0, s1, rlo, rhi);
+    for (int64_t c = s0; c < s1; c += 64) {  // wave-uniform bounds
+      const int64_t e = c + lane;
+      int64_t r = -1;
+      if (e < s1) {
+        r = row_of_edge(offs, rlo, rhi, e);
+        const int64_t k = e - offs[r];
+        const int32_t x = changed[r];
+        int32_t u = -1;
+        if (x >= 0 && x < nv) {
+          const int64_t idx = rowptr[x] + k;
+          if (idx < ne) u = tails[idx];
+        } else if (x >= nv && (int64_t)x - nv < ng) {
+          const int64_t idx = g_rowptr[(int64_t)x - nv] + k;
+          if (idx < neg) u = g_heads[idx];
+        }
+        if (u >= 0 && u < nv) active[u] = 1;
+      }
+      const int64_t last_row = __shfl(r, 63, 64);
+      if (last_row >= 0) rlo = last_row;
+    }
+  }
+}
+
+template <bool WRITE>
+__global__ __launch_bounds__(256) void frontier_compact_kernel(
+    const uint8_t* __restrict__ active, const uint8_t* __restrict__ cls,
+    int64_t nv, int64_t nunit, int32_t* __restrict__ unit_cnt,
+    const int32_t* __restrict__ unit_off,
+    const int32_t* __restrict__ class_base, int32_t* __restrict__ lists) {
+  const int lane = threadIdx.x % 64;
+  const int64_t unit = (int64_t)blockIdx.x * (blockDim.x / 64) +
+                       threadIdx.x / 64;
+  if (unit >= nunit) return;  // wave-uniform
+  int32_t run[FC_CLASSES];
+#pragma unroll
+  for (int c = 0; c < FC_CLASSES; c++)
+    run[c] = WRITE ? class_base[c] + unit_off[unit * FC_CLASSES + c] : 0;
+  const uint64_t below = ((uint64_t)1 << lane) - 1;
+  const int64_t v0 = unit * FC_UNIT;
+  for (int i = 0; i < FC_ITEMS; i++) {
+    const int64_t v = v0 + (int64_t)i * 64 + lane;
+    int k = -1;
+    if (v < nv && active[v]) k = cls[v];
+#pragma unroll
+    for (int c = 0; c < FC_CLASSES; c++) {
+      const uint64_t m = __ballot(k == c);
+      if (WRITE && k == c) {
+        // all lists together hold at most nv ids (memory-safety guard)
+        const int64_t idx = (int64_t)run[c] + __popcll(m & below);
+        if (idx < nv) lists[idx] = (int32_t)v;
+      }
+      run[c] += __popcll(m);
+    }
+  }
+  if (!WRITE && lane == 0) {
+#pragma unroll
+    for (int c = 0; c < FC_CLASSES; c++)
+      unit_cnt[unit * FC_CLASSES + c] = run[c];
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Hub candidate generation via rocPRIM: gather the neighbours' community
 // ids, then a per-hub segmented radix sort of those keys (only
 // ceil(log2 C) bits) with the edge weights as payload. The torch fallback
@@ -1525,6 +1664,51 @@ void launch_cc_compress(int32_t* comp, int64_t nl, hipStream_t stream) {
   if (nl == 0) return;
   hipLaunchKernelGGL(cc_compress_kernel, dim3(grid_for(nl, 256)), dim3(256),
                      0, stream, comp, nl);
+}
+
+// Degrees of the changed rows into deg_out; marks the changed locals.
+void launch_frontier_degrees(const FrontierArgs& a, int64_t* deg_out,
+                             hipStream_t stream) {
+  if (a.nc == 0) return;
+  hipLaunchKernelGGL(frontier_degrees_kernel, dim3(grid_for(a.nc, 256)),
+                     dim3(256), 0, stream, a.changed, a.nc, a.rowptr, a.nv,
+                     a.g_rowptr, a.ng, deg_out, a.active);
+}
+
+// The edge total offs[nc] stays on the device: the grid is sized by the
+// host-side bound `edge_bound` on it (capped; the waves stride over spans).
+void launch_frontier_expand(const FrontierArgs& a, const int64_t* offs,
+                            int64_t edge_bound, hipStream_t stream) {
+  if (a.nc == 0 || edge_bound <= 0) return;
+  constexpr int BLOCK = 256;
+  const int64_t nspan = (edge_bound + FX_SPAN - 1) / FX_SPAN;
+  int grid = grid_for(nspan * 64, BLOCK);
+  if (grid > 2048) grid = 2048;
+  hipLaunchKernelGGL((frontier_expand_kernel<BLOCK>), dim3(grid), dim3(BLOCK),
+                     0, stream, a.changed, a.nc, offs, a.rowptr, a.tails, a.nv,
+                     a.ne, a.g_rowptr, a.g_heads, a.ng, a.neg, a.active);
+}
+
+int frontier_span() { return FX_SPAN; }
+int frontier_classes() { return FC_CLASSES; }
+int64_t frontier_units(int64_t nv) { return (nv + FC_UNIT - 1) / FC_UNIT; }
+
+void launch_frontier_compact(const uint8_t* active, const uint8_t* cls,
+                             int64_t nv, int32_t* unit_cnt,
+                             const int32_t* unit_off,
+                             const int32_t* class_base, int32_t* lists,
+                             bool write, hipStream_t stream) {
+  const int64_t nunit = frontier_units(nv);
+  if (nunit == 0) return;
+  const int grid = (int)((nunit + 3) / 4);  // 4 waves per 256-thread block
+  if (write)
+    hipLaunchKernelGGL(frontier_compact_kernel<true>, dim3(grid), dim3(256), 0,
+                       stream, active, cls, nv, nunit, unit_cnt, unit_off,
+                       class_base, lists);
+  else
+    hipLaunchKernelGGL(frontier_compact_kernel<false>, dim3(grid), dim3(256),
+                       0, stream, active, cls, nv, nunit, unit_cnt, unit_off,
+                       class_base, lists);
 }
 
 // rocPRIM wrappers (two-phase: bytes query with temp==nullptr, then run).
