@@ -20,6 +20,8 @@ from .refine import RefineReport, refine_coin, refine_partition
 from .dynamic import (EdgeBatch, FrontierReport, affected_vertices,
                       apply_edge_batch, frontier_expand_torch,
                       frontier_move_torch, run_frontier_phase)
+from .uncoarsen import (VcycleLevel, intra_boundary_torch,
+                        run_uncoarsen_phase)
 
 __all__ = [
     "Graph",
@@ -44,5 +46,8 @@ __all__ = [
     "run_frontier_phase",
     "frontier_move_torch",
     "frontier_expand_torch",
+    "VcycleLevel",
+    "intra_boundary_torch",
+    "run_uncoarsen_phase",
     "__version__",
 ]

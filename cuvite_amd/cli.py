@@ -140,6 +140,12 @@ def build_parser() -> argparse.ArgumentParser:
                     "result always passes through the final split "
                     "(--connectivity final is implied, level is rejected; "
                     "-p skips refinement)")
+    ap.add_argument("--vcycle", action="store_true",
+                    help="keep every level on the way down and refine the "
+                    "partition level by level on the way back up to the "
+                    "input graph (never lowers the exact modularity; costs "
+                    "the memory of the kept levels; not with --leiden or "
+                    "--connectivity level)")
     ap.add_argument("--check-connected", action="store_true",
                     help="print how many communities of the partition (the "
                     "returned one, or the one --score-communities reads) "
@@ -158,6 +164,9 @@ def validate(args, world: int):
         sys.exit("Cannot enable both -p and -i")
     if args.leiden and args.connectivity == "level":
         sys.exit("Cannot enable both --leiden and --connectivity level")
+    if args.vcycle and (args.leiden or args.connectivity == "level"):
+        sys.exit("Cannot combine --vcycle with --leiden or --connectivity "
+                 "level")
     if args.update_edges:
         if not args.init_communities:
             sys.exit("--update-edges needs --init-communities")
@@ -389,6 +398,7 @@ def main(argv=None) -> int:
         verbose=args.verbose,
         connectivity=args.connectivity,
         algorithm="leiden" if args.leiden else "louvain",
+        vcycle=args.vcycle,
     )
     if args.max_phases:
         cfg.max_phases = args.max_phases
@@ -427,6 +437,11 @@ def main(argv=None) -> int:
                       f"communities={rep.num_communities} "
                       f"subcommunities={rep.num_subcommunities} "
                       f"rounds={rep.rounds}")
+        for lv in res.vcycle or []:
+            print(f"V-cycle: level={lv.level} vertices={lv.nv_global} "
+                  f"boundary={lv.boundary} sweeps={lv.sweeps} "
+                  f"evaluated={lv.evaluated} moved={lv.moved} "
+                  f"Q={lv.q_before:.15g}->{lv.q_after:.15g}")
         if args.leiden and res.connectivity is not None:
             print(f"Final split: communities="
                   f"{res.connectivity.num_communities} "

@@ -48,20 +48,15 @@ def _owner_lookup(comm: Comm, part: Partition, query: torch.Tensor,
     return torch.cat([back[p] for p in range(comm.world)])
 
 
-def coarsen(dg: DistGraph, comm: Comm, cvect: torch.Tensor,
-            halo=None
-            ) -> Tuple[DistGraph, Callable[[torch.Tensor], torch.Tensor]]:
-    """Build the next-level graph from community labels `cvect` (int64 [nv],
-    global old-community ids). Returns (new DistGraph for this rank, renum)
-    where renum maps any tensor of old community gids to new vertex gids
-    (collective: all ranks must call it together with their own queries).
-    `halo`: reuse the phase's HaloContext (ghost set is label-independent,
-    so the rebuild is redundant)."""
+def number_survivors(dg: DistGraph, comm: Comm, cvect: torch.Tensor):
+    """Dense new ids for the labels that occur in `cvect` (int64 [nv], global
+    ids in [0, nv_global)), ascending in the old id: step 1 of the module
+    docstring. Collective. Returns (renum, reply_newid, new_offsets): renum
+    maps any tensor of surviving old gids to new gids (collective),
+    reply_newid answers for gids this rank owns, new_offsets (int64
+    [world + 1], host) are the rank bounds of the new ids."""
     dev = dg.g.device
-    base, bound = dg.base, dg.bound
     world, rank = comm.world, comm.rank
-
-    # --- 1. survivors to owners; owners number their own ---------------------
     my_labels = torch.unique(cvect)  # sorted
     if world == 1:
         survivors = my_labels
@@ -78,9 +73,6 @@ def coarsen(dg: DistGraph, comm: Comm, cvect: torch.Tensor,
     new_offsets = torch.zeros(world + 1, dtype=torch.int64)
     new_offsets[1:] = torch.cumsum(counts.cpu(), dim=0)
     my_off = int(new_offsets[rank])
-    gnc = int(new_offsets[-1])
-    assert gnc < (1 << 31), "coarse graph must have < 2^31 communities"
-    new_part = Partition.from_bounds(new_offsets)
 
     def reply_newid(gids: torch.Tensor) -> torch.Tensor:
         return my_off + torch.searchsorted(survivors, gids)
@@ -91,6 +83,27 @@ def coarsen(dg: DistGraph, comm: Comm, cvect: torch.Tensor,
         out = torch.empty_like(vals)
         out[order] = vals
         return out
+
+    return renum, reply_newid, new_offsets
+
+
+def coarsen(dg: DistGraph, comm: Comm, cvect: torch.Tensor,
+            halo=None
+            ) -> Tuple[DistGraph, Callable[[torch.Tensor], torch.Tensor]]:
+    """Build the next-level graph from community labels `cvect` (int64 [nv],
+    global old-community ids). Returns (new DistGraph for this rank, renum)
+    where renum maps any tensor of old community gids to new vertex gids
+    (collective: all ranks must call it together with their own queries).
+    `halo`: reuse the phase's HaloContext (ghost set is label-independent,
+    so the rebuild is redundant)."""
+    dev = dg.g.device
+    world, rank = comm.world, comm.rank
+
+    # --- 1. survivors to owners; owners number their own ---------------------
+    renum, reply_newid, new_offsets = number_survivors(dg, comm, cvect)
+    gnc = int(new_offsets[-1])
+    assert gnc < (1 << 31), "coarse graph must have < 2^31 communities"
+    new_part = Partition.from_bounds(new_offsets)
 
     # --- 2. resolve new ids for all referenced communities -------------------
     if halo is None:

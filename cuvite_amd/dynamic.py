@@ -138,6 +138,145 @@ def _check_frontier(dg: DistGraph, comm: Comm, mask) -> None:
                          "per local vertex on every rank")
 
 
+class FrontierSweeps:
+    """The sweep both frontier phases run, in steps the caller orders:
+    run_frontier_phase below (stop test on the convergence estimate, after
+    the aggregate update) and uncoarsen.run_uncoarsen_phase (stop test on the
+    exact Q, before it).
+
+    Construction sets up PhaseState(init_labels=prev) and one edge pass under
+    `prev`: cw for ALL vertices and the ghost -> local adjacency. The first
+    frontier is the mask `frontier0` (bool [nv]) or, with `boundary=True`,
+    the boundary of `prev`: every vertex with a neighbour of another label,
+    from the same edge pass (ops.intra_boundary)."""
+
+    def __init__(self, dg: DistGraph, comm: Comm, cfg, prev: torch.Tensor,
+                 frontier0: Optional[torch.Tensor] = None, halo=None, *,
+                 boundary: bool = False, expand: bool = True,
+                 observe: Optional[Callable] = None, timers=None):
+        from .louvain import PhaseState
+        dev = dg.g.device
+        self.dg, self.comm, self.cfg = dg, comm, cfg
+        self.use_hip = _use_hip(cfg.backend, dev)
+        self.state = state = PhaseState(dg, comm, halo=halo, init_labels=prev)
+        state.use_hip = self.use_hip
+        if not boundary:
+            _check_frontier(dg, comm, frontier0)
+        self.expand, self.observe, self.timers = expand, observe, timers
+        if self.use_hip:
+            from . import ops
+            self.ops = ops
+        hl = state.halo
+        rowptr, tails, weights = dg.g.rowptr, hl.tails_dense, dg.g.weights
+
+        self.ghost = exchange_ghost_labels(hl, state.curr_comm)
+        all_labels = torch.cat([state.curr_comm, self.ghost])
+        if not boundary:
+            if self.use_hip:
+                self.cw = ops.intra_weight(rowptr, tails, weights, all_labels)
+            else:
+                self.cw = intra_weight_torch(rowptr, tails, weights,
+                                             all_labels).to(weights.dtype)
+            self.active = frontier0.to(dev).clone()
+        else:
+            if self.use_hip:
+                self.cw, mask = ops.intra_boundary(rowptr, tails, weights,
+                                                   all_labels)
+            else:
+                from .uncoarsen import intra_boundary_torch
+                self.cw, mask = intra_boundary_torch(rowptr, tails, weights,
+                                                     all_labels)
+                self.cw = self.cw.to(weights.dtype)
+            self.active = mask.to(torch.bool)
+        del all_labels
+        state.cluster_weight = self.cw
+        self.g_rowptr, self.g_heads = ghost_reverse_csr(rowptr, tails, hl.ng)
+        self.moved = None           # local vertices whose label changed in
+        #                             the last sweep adopted
+        self._ghost_prev = self.ghost  # ghost labels as of the previous
+        #                                sweep's exchange
+        self._remote_gids = None
+
+    def span(self, name):
+        import contextlib
+        return self.timers(name) if self.timers is not None \
+            else contextlib.nullcontext()
+
+    def move(self, sweep: int):
+        """Sweep `sweep` (1-based) up to and including the move: ghost
+        exchange, the next frontier (moved + N(moved), changed ghosts
+        included) from sweep 2 on, densify, frontier_move. Returns (target
+        global labels [nv], global frontier size). Afterwards self.cw /
+        state.cluster_weight hold cw under state.curr_comm for every vertex;
+        the aggregates are still the ones the sweep read."""
+        state, dg, comm = self.state, self.dg, self.comm
+        from .louvain import _dense_to_gid
+        dev = dg.g.device
+        nv = dg.nv
+        hl = state.halo
+        rowptr, tails, weights = dg.g.rowptr, hl.tails_dense, dg.g.weights
+        with self.span("exchange"):
+            if sweep > 1:
+                self.ghost = exchange_ghost_labels(hl, state.curr_comm)
+        ghost = self.ghost
+        if sweep > 1 and self.expand:
+            with self.span("expand"):
+                ch = [self.moved.nonzero(as_tuple=True)[0]]
+                if hl.ng:
+                    ch.append(nv + (ghost != self._ghost_prev).nonzero(
+                        as_tuple=True)[0])
+                changed = torch.cat(ch).to(torch.int32)
+                self.active = torch.zeros(nv, dtype=torch.bool, device=dev)
+                if self.use_hip:
+                    self.ops.frontier_expand(changed, rowptr, tails,
+                                             self.g_rowptr, self.g_heads,
+                                             self.active)
+                else:
+                    frontier_expand_torch(changed, rowptr, tails,
+                                          self.g_rowptr, self.g_heads,
+                                          self.active)
+        self._ghost_prev = ghost
+        active = self.active
+        if self.observe is not None:
+            self.observe("begin", sweep=sweep, active=active.clone(),
+                         curr=state.curr_comm.clone(), ghost=ghost.clone(),
+                         cw=self.cw.clone())
+        with self.span("densify"):
+            dense, remote_gids, c_size, c_degree, c_gid = state.densify(ghost)
+            inp = MoveInputs(rowptr, tails, weights, dense, state.v_degree,
+                             c_size, c_degree, c_gid, state.constant,
+                             local_gid_base=dg.base)
+        if self.use_hip:
+            with self.span("compact"):
+                lists = self.ops.frontier_lists(rowptr, active)
+                n_act = sum(int(v.numel()) for v in lists)
+            with self.span("move"):
+                tgt_dense, self.cw = self.ops.frontier_move(
+                    inp, active, self.cw, lists=lists)
+        else:
+            n_act = int(active.sum())
+            tgt_dense, self.cw = frontier_move_torch(inp, active, self.cw)
+        state.cluster_weight = self.cw
+        self._remote_gids = remote_gids
+        target = _dense_to_gid(state, tgt_dense, remote_gids)
+        if comm.world > 1:
+            n_act = int(comm.allreduce_scalar(float(n_act)))
+        return target, n_act
+
+    def apply(self, target: torch.Tensor) -> None:
+        """The aggregate update for `target` (what move returned), on the
+        delta path: the fused next_size / next_degree accounting counts
+        visited vertices only."""
+        with self.span("aggregates"):
+            self.state.apply_moves(target, self._remote_gids, recount=False)
+
+    def adopt(self, target: torch.Tensor) -> None:
+        """Make `target` the current labels (run_phase's rotation)."""
+        state = self.state
+        self.moved = target != state.curr_comm
+        state.past_comm, state.curr_comm = state.curr_comm, target
+
+
 def run_frontier_phase(dg: DistGraph, comm: Comm, cfg, prev: torch.Tensor,
                        frontier0: torch.Tensor, halo=None, *,
                        lower: float = -1.0,
@@ -158,40 +297,13 @@ def run_frontier_phase(dg: DistGraph, comm: Comm, cfg, prev: torch.Tensor,
     `observe(event, **state)`: test hook, called with "begin" once the
     sweep's frontier is known and with "end" after its move. `timers`: a
     utils.timers.Timers that accumulates the parts of a sweep."""
-    from .louvain import PhaseState, _dense_to_gid, _modularity
-    import contextlib
+    from .louvain import _modularity
 
-    dev = dg.g.device
-    use_hip = _use_hip(cfg.backend, dev)
-    state = PhaseState(dg, comm, halo=halo, init_labels=prev)
-    state.use_hip = use_hip
-    _check_frontier(dg, comm, frontier0)
+    sw = FrontierSweeps(dg, comm, cfg, prev, frontier0, halo, expand=expand,
+                        observe=observe, timers=timers)
+    state = sw.state
     if threshold is None:
         threshold = cfg.threshold
-    if use_hip:
-        from . import ops
-
-    def span(name):
-        return timers(name) if timers is not None else contextlib.nullcontext()
-
-    nv = dg.nv
-    hl = state.halo
-    rowptr, tails, weights = dg.g.rowptr, hl.tails_dense, dg.g.weights
-    W = weights.dtype
-
-    # cw for ALL vertices under prev, and the ghost -> local adjacency
-    ghost = exchange_ghost_labels(hl, state.curr_comm)
-    all_labels = torch.cat([state.curr_comm, ghost])
-    if use_hip:
-        cw = ops.intra_weight(rowptr, tails, weights, all_labels)
-    else:
-        cw = intra_weight_torch(rowptr, tails, weights, all_labels).to(W)
-    del all_labels
-    g_rowptr, g_heads = ghost_reverse_csr(rowptr, tails, hl.ng)
-
-    active = frontier0.to(dev).clone()
-    moved = None          # local vertices whose label changed last sweep
-    ghost_prev = ghost    # ghost labels as of the previous sweep's exchange
     prev_mod = lower
     iters = 0
     sizes: List[int] = []
@@ -199,56 +311,15 @@ def run_frontier_phase(dg: DistGraph, comm: Comm, cfg, prev: torch.Tensor,
 
     while iters < cfg.max_iters_per_phase:
         iters += 1
-        with span("exchange"):
-            if iters > 1:
-                ghost = exchange_ghost_labels(hl, state.curr_comm)
-        if iters > 1 and expand:
-            with span("expand"):
-                ch = [moved.nonzero(as_tuple=True)[0]]
-                if hl.ng:
-                    ch.append(nv + (ghost != ghost_prev).nonzero(
-                        as_tuple=True)[0])
-                changed = torch.cat(ch).to(torch.int32)
-                active = torch.zeros(nv, dtype=torch.bool, device=dev)
-                if use_hip:
-                    ops.frontier_expand(changed, rowptr, tails, g_rowptr,
-                                        g_heads, active)
-                else:
-                    frontier_expand_torch(changed, rowptr, tails, g_rowptr,
-                                          g_heads, active)
-        ghost_prev = ghost
-        if observe is not None:
-            observe("begin", sweep=iters, active=active.clone(),
-                    curr=state.curr_comm.clone(), ghost=ghost.clone(),
-                    cw=cw.clone())
-        with span("densify"):
-            dense, remote_gids, c_size, c_degree, c_gid = state.densify(ghost)
-            inp = MoveInputs(rowptr, tails, weights, dense, state.v_degree,
-                             c_size, c_degree, c_gid, state.constant,
-                             local_gid_base=dg.base)
-        if use_hip:
-            with span("compact"):
-                lists = ops.frontier_lists(rowptr, active)
-                n_act = sum(int(v.numel()) for v in lists)
-            with span("move"):
-                tgt_dense, cw = ops.frontier_move(inp, active, cw, lists=lists)
-        else:
-            n_act = int(active.sum())
-            tgt_dense, cw = frontier_move_torch(inp, active, cw)
-        with span("aggregates"):
-            target = _dense_to_gid(state, tgt_dense, remote_gids)
-            state.cluster_weight = cw
-            # the delta path: the fused next_size / next_degree accounting
-            # counts visited vertices only
-            state.apply_moves(target, remote_gids, recount=False)
-        with span("modularity"):
+        target, n_act = sw.move(iters)
+        sw.apply(target)
+        with sw.span("modularity"):
             curr_mod = _modularity(state)
-        sizes.append(int(comm.allreduce_scalar(float(n_act)))
-                     if comm.world > 1 else n_act)
+        sizes.append(n_act)
         estimates.append(curr_mod)
         if observe is not None:
-            observe("end", sweep=iters, target=target.clone(), cw=cw.clone(),
-                    estimate=curr_mod)
+            observe("end", sweep=iters, target=target.clone(),
+                    cw=sw.cw.clone(), estimate=curr_mod)
         if cfg.verbose and comm.rank == 0:
             print(f"  frontier sweep {iters}: |A|={sizes[-1]} "
                   f"Q={curr_mod:.6f}")
@@ -257,8 +328,7 @@ def run_frontier_phase(dg: DistGraph, comm: Comm, cfg, prev: torch.Tensor,
         if (curr_mod - prev_mod) < threshold:
             break
         prev_mod = max(curr_mod, lower)
-        moved = target != state.curr_comm
-        state.past_comm, state.curr_comm = state.curr_comm, target
+        sw.adopt(target)
 
     report = FrontierReport(sizes, sum(sizes), iters, estimates)
     return prev_mod, state.past_comm, iters, state.halo, report

@@ -75,6 +75,13 @@ class LouvainConfig:
     #     only.
     refine_max_rounds: int = REFINE_MAX_ROUNDS
     refine_seed: int = 0
+    vcycle: bool = False
+    #   keep every accepted level (graph, halo, map to the next level) and,
+    #   after the last phase, refine the partition level by level on the way
+    #   back to the input graph (uncoarsen.refine_up). Never lowers the exact
+    #   modularity; costs the memory of the kept levels. Cannot be combined
+    #   with algorithm="leiden" or connectivity="level": moves on the way up
+    #   would break the connectivity those promise.
 
 
 @dataclass
@@ -94,6 +101,10 @@ class LouvainResult:
     connectivity: Optional[ConnectivityReport] = None  # "final": the report
     #   of the split (`communities` are its labels); "level": the report of
     #   the last phase's split (every level entry carries its own)
+    vcycle: Optional[list] = None  # vcycle=True: one uncoarsen.VcycleLevel
+    #   per refined level, coarsest first; `modularity` stays the way down's
+    #   estimate, the last entry's q_after is the exact Q of `communities`
+    #   (before any final split)
 
     @property
     def teps_numerator(self) -> float:
@@ -682,7 +693,9 @@ def louvain(dg: DistGraph, comm: Optional[Comm] = None,
     the moved vertices and their neighbours. levels[0]["frontier"] carries
     the FrontierReport. Coloring, ordering, early termination and threshold
     scaling cannot be combined with it; one_phase, connectivity and
-    algorithm="leiden" act after the phase and compose unchanged."""
+    algorithm="leiden" act after the phase and compose unchanged.
+    `cfg.vcycle`: see LouvainConfig; the way up starts when the loop below
+    ends and replaces the composed labels."""
     from .coarsen import coarsen, remap_labels
     from .coloring import distance1_coloring
 
@@ -705,6 +718,14 @@ def louvain(dg: DistGraph, comm: Optional[Comm] = None,
     if leiden and cfg.connectivity == "level":
         raise ValueError("algorithm='leiden' refines every level itself; "
                          "connectivity='level' cannot be combined with it")
+    if cfg.vcycle and (leiden or cfg.connectivity == "level"):
+        raise ValueError("vcycle moves vertices on the way up and cannot "
+                         "keep the connectivity that algorithm='leiden' and "
+                         "connectivity='level' promise")
+    hier = None
+    if cfg.vcycle:
+        from .uncoarsen import Hierarchy, refine_up
+        hier = Hierarchy()
     conn_report = None
 
     def split_level(cvect, level_halo, entry):
@@ -784,6 +805,8 @@ def louvain(dg: DistGraph, comm: Optional[Comm] = None,
             orig_assign = remap_labels(level, comm, orig_vertex if leiden
                                        else orig_assign, cvect)
             mods.append(curr_mod)
+            if hier is not None:
+                hier.push(level, phase_halo, cvect)
             if cfg.one_phase:
                 break
             t0 = time.perf_counter()
@@ -814,6 +837,8 @@ def louvain(dg: DistGraph, comm: Optional[Comm] = None,
                 level, renum = coarsen(level, comm, cvect, halo=phase_halo)
                 # cvect-composed orig_assign holds OLD comm gids; renumber
                 orig_assign = renum(orig_assign)
+                if hier is not None:
+                    hier.maps[-1] = renum(cvect)
             phase_halo = None  # free the ghost structure before next phase
             level_entry["rebuild_s"] = time.perf_counter() - t0
             times["rebuild"] += level_entry["rebuild_s"]
@@ -832,6 +857,8 @@ def louvain(dg: DistGraph, comm: Optional[Comm] = None,
                         cvect)
                     mods.append(curr_mod2)
                     curr_mod = curr_mod2
+                    if hier is not None:
+                        hier.push(level, phase_halo, cvect)
             break
 
         prev_mod = curr_mod
@@ -842,15 +869,28 @@ def louvain(dg: DistGraph, comm: Optional[Comm] = None,
         if phase >= cfg.max_phases or tot_iters > MAX_TOTAL_ITERS:
             break
 
+    # the input graph's halo is still there only if no coarsening took it over
+    final_halo = phase_halo if level is dg else None
+    vcycle_report = None
+    if hier is not None:
+        vcycle_report = []
+        if len(hier):
+            t0 = time.perf_counter()
+            # the last level built may be one no phase gained on: the way up
+            # does not visit it. The input graph's halo outlives the walk.
+            final_halo = hier.halos[0]
+            level = phase_halo = None
+            orig_assign, vcycle_report = refine_up(hier, comm, cfg)
+            times["vcycle"] = time.perf_counter() - t0
+
     if cfg.connectivity == "final" or leiden:
-        # on the INPUT graph; its halo is still there only if no coarsening
-        # took it over
-        conn_report = split_disconnected(
-            dg, orig_assign, comm, halo=phase_halo if level is dg else None,
-            backend=cfg.backend)
+        # on the INPUT graph
+        conn_report = split_disconnected(dg, orig_assign, comm,
+                                         halo=final_halo,
+                                         backend=cfg.backend)
         orig_assign = conn_report.labels
 
     times["total"] = time.perf_counter() - t_start
     final_mod = mods[-1] if mods else max(prev_mod, curr_mod)
     return LouvainResult(final_mod, orig_assign, phase + 1, tot_iters,
-                         times, mods, levels, conn_report)
+                         times, mods, levels, conn_report, vcycle_report)

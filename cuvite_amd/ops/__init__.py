@@ -652,6 +652,17 @@ def intra_weight(rowptr: torch.Tensor, tails_dense: torch.Tensor,
     return _require().intra_weight(rowptr, tails_dense, weights, labels)
 
 
+def intra_boundary(rowptr: torch.Tensor, tails_dense: torch.Tensor,
+                   weights: torch.Tensor, labels: torch.Tensor):
+    """(cw, mask) from one edge pass: cw is intra_weight's result bit for
+    bit, mask (uint8 [nv]) is 1 for every row with an edge whose tail lies
+    inside `labels` and carries another label than the row: the boundary
+    vertices, the only ones a local move can move (twin:
+    uncoarsen.intra_boundary_torch). Self-loops and out-of-range tails mark
+    nothing."""
+    return _require().intra_boundary(rowptr, tails_dense, weights, labels)
+
+
 def intra_weight_span() -> int:
     """Edges per wave span of the intra_weight kernel (rows cut by a span
     boundary take the atomic path; tests build their shapes around it)."""

@@ -589,9 +589,12 @@ at::Tensor row_sum(at::Tensor rowptr, at::Tensor weights) {
 }
 
 // Per-vertex weight into the vertex's own community for arbitrary labels
-// (see intra_weight_kernel). labels: int32 or int64, [nv + ng].
-at::Tensor intra_weight(at::Tensor rowptr, at::Tensor tails,
-                        at::Tensor weights, at::Tensor labels) {
+// (see intra_weight_kernel). labels: int32 or int64, [nv + ng]. With `mark`
+// the same pass also fills the boundary mask (uint8 [nv], second result);
+// without it the second result is undefined.
+static std::tuple<at::Tensor, at::Tensor> intra_weight_impl(
+    at::Tensor rowptr, at::Tensor tails, at::Tensor weights,
+    at::Tensor labels, bool mark) {
   CHECK_INPUT(rowptr);
   CHECK_INPUT(tails);
   CHECK_INPUT(weights);
@@ -607,22 +610,46 @@ at::Tensor intra_weight(at::Tensor rowptr, at::Tensor tails,
   TORCH_CHECK(nv < (int64_t)INT32_MAX, "nv exceeds the int32 dense id range");
   TORCH_CHECK(labels.numel() >= nv, "labels must cover all local vertices");
   auto out = at::zeros({nv}, weights.options());
+  at::Tensor mask;
+  if (mark) mask = at::zeros({nv}, rowptr.options().dtype(at::kByte));
   auto stream = at::hip::getCurrentHIPStream().stream();
   AT_DISPATCH_FLOATING_TYPES(weights.scalar_type(), "intra_weight", [&] {
     using W = scalar_t;
+    auto run = [&](auto* lab) {
+      using L = std::remove_const_t<std::remove_pointer_t<decltype(lab)>>;
+      if (mark)
+        cuvite::launch_intra_boundary<W, L>(
+            rowptr.data_ptr<int64_t>(), tails.data_ptr<int32_t>(),
+            weights.data_ptr<W>(), lab, nv, tails.numel(), labels.numel(),
+            out.data_ptr<W>(), mask.data_ptr<uint8_t>(), stream);
+      else
+        cuvite::launch_intra_weight<W, L>(
+            rowptr.data_ptr<int64_t>(), tails.data_ptr<int32_t>(),
+            weights.data_ptr<W>(), lab, nv, tails.numel(), labels.numel(),
+            out.data_ptr<W>(), stream);
+    };
     if (labels.scalar_type() == at::kInt)
-      cuvite::launch_intra_weight<W, int32_t>(
-          rowptr.data_ptr<int64_t>(), tails.data_ptr<int32_t>(),
-          weights.data_ptr<W>(), labels.data_ptr<int32_t>(), nv,
-          tails.numel(), labels.numel(), out.data_ptr<W>(), stream);
+      run(labels.data_ptr<int32_t>());
     else
-      cuvite::launch_intra_weight<W, int64_t>(
-          rowptr.data_ptr<int64_t>(), tails.data_ptr<int32_t>(),
-          weights.data_ptr<W>(), labels.data_ptr<int64_t>(), nv,
-          tails.numel(), labels.numel(), out.data_ptr<W>(), stream);
+      run(labels.data_ptr<int64_t>());
   });
   C10_HIP_CHECK(hipGetLastError());
-  return out;
+  return {out, mask};
+}
+
+at::Tensor intra_weight(at::Tensor rowptr, at::Tensor tails,
+                        at::Tensor weights, at::Tensor labels) {
+  return std::get<0>(intra_weight_impl(rowptr, tails, weights, labels, false));
+}
+
+// intra_weight and, from the same edge pass, the boundary mask: mask[v] = 1
+// iff row v holds an edge whose tail lies inside `labels` and carries another
+// label than v. Returns (cw [nv], mask uint8 [nv]).
+std::tuple<at::Tensor, at::Tensor> intra_boundary(at::Tensor rowptr,
+                                                  at::Tensor tails,
+                                                  at::Tensor weights,
+                                                  at::Tensor labels) {
+  return intra_weight_impl(rowptr, tails, weights, labels, true);
 }
 
 // Connected components of the graph restricted to edges whose endpoints
@@ -814,6 +841,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fresh community size/degree recount from labels (HIP)");
   m.def("intra_weight", &intra_weight,
         "per-vertex weight into the own community, edge-balanced (HIP)");
+  m.def("intra_boundary", &intra_boundary,
+        "intra_weight plus the uint8 boundary mask, in one edge pass");
   m.def("intra_weight_span", &cuvite::intra_weight_span,
         "edges per wave span of the intra_weight kernel");
   m.def("cc_components", &cc_components,

@@ -126,6 +126,13 @@ template <typename W, typename L>
 void launch_intra_weight(const int64_t* rowptr, const int32_t* tails,
                          const W* weights, const L* labels, int64_t nv,
                          int64_t ne, int64_t nl, W* out, hipStream_t stream);
+// intra_weight plus mask[v] = 1 for every row with an in-range tail of
+// another label; `out` and `mask` (uint8 [nv]) zero-initialised by the caller.
+template <typename W, typename L>
+void launch_intra_boundary(const int64_t* rowptr, const int32_t* tails,
+                           const W* weights, const L* labels, int64_t nv,
+                           int64_t ne, int64_t nl, W* out, uint8_t* mask,
+                           hipStream_t stream);
 int intra_weight_span();
 // The caller zeroes `changed` first.
 template <typename L>

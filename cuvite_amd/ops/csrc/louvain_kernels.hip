@@ -738,11 +738,19 @@ DEV_INLINE void span_row_range(const int64_t* __restrict__ rowptr, int64_t nv,
   rhi = (rhi + step - 1 < nv - 1) ? rhi + step - 1 : nv - 1;
 }
 
-template <typename W, typename L, int BLOCK>
+// MARK: the same pass also flags the boundary vertices, mask[row] = 1 for
+// every row with an edge whose tail is inside the label array and carries
+// another label (the first frontier of an uncoarsening phase). The flag is a
+// plain byte store by the lane that holds the edge: every writer stores the
+// same 1 into a caller-zeroed array, so the order of the writers does not
+// matter (frontier_expand_kernel's marks). Self-loops compare equal and
+// out-of-range tails are skipped, so neither marks anything. Without MARK
+// `mask` is null and never read.
+template <typename W, typename L, int BLOCK, bool MARK>
 __global__ __launch_bounds__(BLOCK) void intra_weight_kernel(
     const int64_t* __restrict__ rowptr, const int32_t* __restrict__ tails,
     const W* __restrict__ weights, const L* __restrict__ labels, int64_t nv,
-    int64_t ne, int64_t nl, W* __restrict__ out) {
+    int64_t ne, int64_t nl, W* __restrict__ out, uint8_t* __restrict__ mask) {
   constexpr int WAVES = BLOCK / 64;
   const int lane = threadIdx.x % 64;
   const int64_t nspan = (ne + IW_SPAN - 1) / IW_SPAN;
@@ -787,7 +795,10 @@ __global__ __launch_bounds__(BLOCK) void intra_weight_kernel(
         if (ok) {
           row = (int32_t)row_of_edge(rowptr, rlo, rhi, e);
           rend = rowptr[(int64_t)row + 1];
-          if (inb[k] && lt[k] == labels[row]) val = (double)w[k];
+          if (inb[k]) {
+            if (lt[k] == labels[row]) val = (double)w[k];
+            else if (MARK) mask[row] = 1;  // row < nv: inside the mask
+          }
         }
         if (lane == 0 && row == carry_row) val += carry_val;
         // segmented inclusive scan: equal rows are contiguous lanes
@@ -1623,14 +1634,34 @@ void launch_intra_weight(const int64_t* rowptr, const int32_t* tails,
   if (nv == 0 || ne == 0) return;
   constexpr int BLOCK = 256;
   const int64_t nspan = (ne + IW_SPAN - 1) / IW_SPAN;
-  hipLaunchKernelGGL((intra_weight_kernel<W, L, BLOCK>),
+  hipLaunchKernelGGL((intra_weight_kernel<W, L, BLOCK, false>),
                      dim3(grid_for(nspan * 64, BLOCK)), dim3(BLOCK), 0, stream,
-                     rowptr, tails, weights, labels, nv, ne, nl, out);
+                     rowptr, tails, weights, labels, nv, ne, nl, out,
+                     (uint8_t*)nullptr);
+}
+
+// intra_weight plus the boundary mask (MARK): `out` and `mask` (uint8 [nv])
+// must both be zero-initialised by the caller.
+template <typename W, typename L>
+void launch_intra_boundary(const int64_t* rowptr, const int32_t* tails,
+                           const W* weights, const L* labels, int64_t nv,
+                           int64_t ne, int64_t nl, W* out, uint8_t* mask,
+                           hipStream_t stream) {
+  if (nv == 0 || ne == 0) return;
+  constexpr int BLOCK = 256;
+  const int64_t nspan = (ne + IW_SPAN - 1) / IW_SPAN;
+  hipLaunchKernelGGL((intra_weight_kernel<W, L, BLOCK, true>),
+                     dim3(grid_for(nspan * 64, BLOCK)), dim3(BLOCK), 0, stream,
+                     rowptr, tails, weights, labels, nv, ne, nl, out, mask);
 }
 #define INSTANTIATE_IW(W, L)                                                  \
   template void launch_intra_weight<W, L>(const int64_t*, const int32_t*,    \
                                           const W*, const L*, int64_t,       \
-                                          int64_t, int64_t, W*, hipStream_t);
+                                          int64_t, int64_t, W*, hipStream_t); \
+  template void launch_intra_boundary<W, L>(const int64_t*, const int32_t*,  \
+                                            const W*, const L*, int64_t,     \
+                                            int64_t, int64_t, W*, uint8_t*,  \
+                                            hipStream_t);
 INSTANTIATE_IW(float, int32_t)
 INSTANTIATE_IW(float, int64_t)
 INSTANTIATE_IW(double, int32_t)
