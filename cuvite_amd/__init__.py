@@ -11,7 +11,7 @@ Vite-compatible binary graph I/O.
 __version__ = "0.1.0"
 
 from .graph import Graph, DistGraph, Partition
-from .louvain import louvain, LouvainConfig, LouvainResult
+from .louvain import louvain, LouvainConfig, LouvainResult, resolution_scan
 from .quality import (PartitionQuality, intra_weight_torch,
                       partition_quality)
 from .connectivity import (ConnectivityReport, cc_components_torch,
@@ -30,6 +30,7 @@ __all__ = [
     "louvain",
     "LouvainConfig",
     "LouvainResult",
+    "resolution_scan",
     "PartitionQuality",
     "partition_quality",
     "intra_weight_torch",

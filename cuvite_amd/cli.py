@@ -10,12 +10,14 @@ CPU); single-process runs need no launcher.
 Examples:
     python -m cuvite_amd -f karate.bin -c 8 -i
     python -m cuvite_amd -n 16384 -e 5 -o
+    python -m cuvite_amd --karate --resolution 2 --exact-modularity
     torchrun --standalone --nproc-per-node 8 -m cuvite_amd --rmat 26
 """
 
 from __future__ import annotations
 
 import argparse
+import math
 import sys
 import time
 
@@ -146,6 +148,14 @@ def build_parser() -> argparse.ArgumentParser:
                     "input graph (never lowers the exact modularity; costs "
                     "the memory of the kept levels; not with --leiden or "
                     "--connectivity level)")
+    ap.add_argument("--resolution", metavar="G", type=float, default=None,
+                    help="resolution gamma of the modularity that is "
+                    "optimised and reported, Q = sum_c [in_c/2m - G "
+                    "(a_c/2m)^2] (default 1): above 1 more and smaller "
+                    "communities, below 1 fewer and larger ones. Applies to "
+                    "the run in every mode and to --score-communities, "
+                    "--init-communities, --exact-modularity and "
+                    "--update-edges")
     ap.add_argument("--check-connected", action="store_true",
                     help="print how many communities of the partition (the "
                     "returned one, or the one --score-communities reads) "
@@ -177,6 +187,9 @@ def validate(args, world: int):
                 or args.threshold_cycling):
             sys.exit("--update-edges cannot be combined with -c, -d, -t "
                      "or -i")
+    if args.resolution is not None and not (
+            math.isfinite(args.resolution) and args.resolution > 0.0):
+        sys.exit("--resolution must be a finite number > 0")
     if args.early_term and not 1 <= args.early_term <= 4:
         sys.exit("-t must be 1..4")
     if args.early_term in (2, 4) and not 0.0 <= args.et_alpha <= 1.0:
@@ -343,10 +356,14 @@ def main(argv=None) -> int:
         print_dist_stats(dg, comm)
     if args.just_process:
         return 0
+    gamma = 1.0 if args.resolution is None else args.resolution
+    if args.resolution is not None and comm.rank == 0:
+        print(f"Resolution: {gamma:g}")
 
     if args.score_communities:
         part_labels = _load_partition_slice(args.score_communities, args, dg)
-        pq = partition_quality(dg, part_labels, comm, backend=args.backend)
+        pq = partition_quality(dg, part_labels, comm, backend=args.backend,
+                               resolution=gamma)
         if comm.rank == 0:
             print(f"Partition {args.score_communities}: "
                   f"modularity={pq.modularity:.15g} "
@@ -399,6 +416,7 @@ def main(argv=None) -> int:
         connectivity=args.connectivity,
         algorithm="leiden" if args.leiden else "louvain",
         vcycle=args.vcycle,
+        resolution=gamma,
     )
     if args.max_phases:
         cfg.max_phases = args.max_phases
@@ -410,7 +428,8 @@ def main(argv=None) -> int:
             init_labels = init_labels[vo_order]
             if init_frontier is not None:
                 init_frontier = init_frontier[vo_order]
-        pq = partition_quality(dg, init_labels, comm, backend=args.backend)
+        pq = partition_quality(dg, init_labels, comm, backend=args.backend,
+                               resolution=gamma)
         if comm.rank == 0:
             print(f"Initial partition: modularity={pq.modularity:.15g} "
                   f"communities={pq.num_communities}")
@@ -472,7 +491,7 @@ def main(argv=None) -> int:
         # res.communities labels the graph that was clustered (after
         # --vertex-order degree the relabelled, isomorphic one)
         pq = partition_quality(dg, res.communities, comm,
-                               backend=args.backend)
+                               backend=args.backend, resolution=gamma)
         if comm.rank == 0:
             print(f"Exact modularity: {pq.modularity:.15g} "
                   f"({pq.num_communities} communities)")

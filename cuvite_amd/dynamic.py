@@ -158,7 +158,8 @@ class FrontierSweeps:
         dev = dg.g.device
         self.dg, self.comm, self.cfg = dg, comm, cfg
         self.use_hip = _use_hip(cfg.backend, dev)
-        self.state = state = PhaseState(dg, comm, halo=halo, init_labels=prev)
+        self.state = state = PhaseState(dg, comm, halo=halo, init_labels=prev,
+                                        resolution=cfg.resolution)
         state.use_hip = self.use_hip
         if not boundary:
             _check_frontier(dg, comm, frontier0)

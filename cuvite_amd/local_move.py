@@ -45,7 +45,7 @@ class MoveInputs:
     comm_size: torch.Tensor    # int64 [nc]
     comm_degree: torch.Tensor  # W [nc]
     comm_gid: torch.Tensor     # int64 [nc]  dense comm id -> global comm id
-    constant: float            # 1 / (2m)
+    constant: float            # γ / (2m)
     # Optional promise about comm_gid: comm_gid[i] == local_gid_base + i for
     # i < nv (the locally owned communities). The HIP kernels then compute
     # those ids instead of gathering them; local_move_torch and

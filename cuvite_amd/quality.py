@@ -35,11 +35,21 @@ _EDGE_CHUNK = 1 << 24  # edges per step of the torch oracle
 
 @dataclass
 class PartitionQuality:
-    modularity: float
+    modularity: float     # Q_gamma at `resolution`
     num_communities: int
     intra_weight: float   # sum of edge weight inside communities (directed)
     total_weight: float   # 2m: sum of all weighted degrees
     coverage: float       # intra_weight / total_weight
+    resolution: float = 1.0  # gamma `modularity` was computed under
+    degree_sq: float = 0.0   # sum over communities of deg[c]^2
+
+    def at(self, gamma: float) -> float:
+        """Q under another resolution from the stored sums: one edge pass
+        scores a partition at any number of resolutions. at(self.resolution)
+        is `modularity`, bit for bit."""
+        # same guard as PhaseState.inv_2m: an edgeless graph scores Q = 0
+        c = 1.0 / self.total_weight if self.total_weight > 0.0 else 0.0
+        return self.intra_weight * c - gamma * self.degree_sq * c * c
 
 
 def intra_weight_torch(rowptr: torch.Tensor, tails_dense: torch.Tensor,
@@ -129,9 +139,13 @@ def _use_hip(backend: str, dev: torch.device) -> bool:
 
 def partition_quality(dg: DistGraph, labels: torch.Tensor,
                       comm: Optional[Comm] = None, halo=None,
-                      backend: str = "auto") -> PartitionQuality:
+                      backend: str = "auto",
+                      resolution: float = 1.0) -> PartitionQuality:
     """Exact modularity of `labels` (int64 [nv], this rank's slice, global
-    community ids in [0, nv_global)) on `dg`. Collective: every rank calls it
+    community ids in [0, nv_global)) on `dg`, at `resolution` gamma:
+    Q_gamma = sum_v iw[v] / 2m - gamma sum_c (deg[c] / 2m)^2
+    (PartitionQuality.at rescores under another gamma without a second
+    pass). Collective: every rank calls it
     with its own slice and gets the same result. `halo`: reuse a HaloContext
     already built for `dg`. On a GPU the per-vertex pass is the HIP
     intra_weight kernel (a missing extension raises); backend="torch" forces
@@ -161,10 +175,11 @@ def partition_quality(dg: DistGraph, labels: torch.Tensor,
     comm.allreduce_sum_(parts)
     tw = comm.allreduce_scalar(float(v_degree.to(torch.float64).sum()))
     ncomm = int(comm.allreduce_scalar(float((size > 0).sum())))
-    # same guard as PhaseState.constant: an edgeless graph scores Q = 0
+    # same guard as PhaseState.inv_2m: an edgeless graph scores Q = 0
     c = 1.0 / tw if tw > 0.0 else 0.0
     intra = float(parts[0])
+    gamma = float(resolution)
     return PartitionQuality(
-        modularity=intra * c - float(parts[1]) * c * c,
+        modularity=intra * c - gamma * float(parts[1]) * c * c,
         num_communities=ncomm, intra_weight=intra, total_weight=tw,
-        coverage=intra * c)
+        coverage=intra * c, resolution=gamma, degree_sq=float(parts[1]))

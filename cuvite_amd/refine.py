@@ -25,8 +25,8 @@ first pair in which no vertex moved anywhere (one allreduce per round), or
 at `max_rounds`. Leftover singletons are legal.
 
 This is the greedy variant: Leiden's randomised choice among the positive
-gains, its well-connectedness pre-tests and a resolution parameter are not
-implemented.
+gains and its well-connectedness pre-tests are not implemented. The gain is
+the gamma-gain of the run (`resolution`).
 """
 
 from __future__ import annotations
@@ -83,8 +83,8 @@ def refine_partition(dg: DistGraph, labels: torch.Tensor,
                      backend: str = "auto",
                      max_rounds: int = REFINE_MAX_ROUNDS, seed: int = 0,
                      level: int = 0,
-                     trace: Optional[Callable[[dict], None]] = None
-                     ) -> RefineReport:
+                     trace: Optional[Callable[[dict], None]] = None,
+                     resolution: float = 1.0) -> RefineReport:
     """Refine the communities `labels` (int64 [nv], this rank's slice, global
     ids in [0, nv_global)) of `dg` into connected sub-communities.
     Collective: every rank calls it with its own slice. `halo`: reuse a
@@ -92,6 +92,7 @@ def refine_partition(dg: DistGraph, labels: torch.Tensor,
     kernels (a missing extension raises); backend="torch" forces the torch
     twin. `trace`, if given, is called after every round with
     {"round", "curr", "target"} (this rank's sub labels before and after).
+    `resolution`: gamma of the gain the movers evaluate (LouvainConfig).
 
     The result depends on neither rank count nor partition."""
     from .connectivity import _count_by_community
@@ -109,7 +110,7 @@ def refine_partition(dg: DistGraph, labels: torch.Tensor,
         move_fn = refine_move_torch
 
     # singleton sub labels; sizes and degrees are the sub aggregates
-    state = PhaseState(dg, comm, halo=halo)
+    state = PhaseState(dg, comm, halo=halo, resolution=resolution)
     state.use_hip = use_hip
     halo = state.halo
     nv = dg.nv

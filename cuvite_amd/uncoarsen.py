@@ -15,7 +15,8 @@ accepted level K down to the input graph:
   - the phase stops on the EXACT modularity. The move of sweep j returns cw
     under the labels the sweep started from for every vertex (dynamic.py's
     invariant), and the aggregates it read belong to the same labels, so
-    q_j = sum(cw) c - sum(deg^2) c^2 costs one reduction and one allreduce.
+    q_j = sum(cw) c - gamma sum(deg^2) c^2 (c = 1/2m, gamma =
+    cfg.resolution) costs one reduction and one allreduce.
     The labels with the largest known q are returned; the targets of the last
     sweep have no known Q and are dropped.
 
