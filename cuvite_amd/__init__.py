@@ -17,9 +17,10 @@ from .quality import (PartitionQuality, intra_weight_torch,
 from .connectivity import (ConnectivityReport, cc_components_torch,
                            split_disconnected)
 from .refine import RefineReport, refine_coin, refine_partition
-from .dynamic import (EdgeBatch, FrontierReport, affected_vertices,
-                      apply_edge_batch, frontier_expand_torch,
-                      frontier_move_torch, run_frontier_phase)
+from .dynamic import (EdgeBatch, FrontierReport, StreamError, StreamStep,
+                      affected_vertices, apply_edge_batch,
+                      apply_routed_batch_torch, frontier_expand_torch,
+                      frontier_move_torch, run_frontier_phase, update_stream)
 from .uncoarsen import (VcycleLevel, intra_boundary_torch,
                         run_uncoarsen_phase)
 
@@ -43,6 +44,10 @@ __all__ = [
     "EdgeBatch",
     "FrontierReport",
     "apply_edge_batch",
+    "apply_routed_batch_torch",
+    "update_stream",
+    "StreamStep",
+    "StreamError",
     "affected_vertices",
     "run_frontier_phase",
     "frontier_move_torch",

@@ -117,13 +117,18 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--init-communities", metavar="FILE", default="",
                     help="warm start: begin clustering from the partition "
                     "in FILE instead of singletons (-z applies)")
-    ap.add_argument("--update-edges", metavar="FILE", default="",
+    ap.add_argument("--update-edges", metavar="FILE", action="append",
+                    default=[],
                     help="dynamic update: the graph given by -f or a "
                     "generator is the OLD graph, --init-communities its "
                     "partition; FILE holds the edge changes, one per line, "
                     "'a u v [w]' to add and 'd u v' to delete (0-based ids, "
                     "# comments). Phase 0 then sweeps only the affected "
-                    "vertices and what their moves reach")
+                    "vertices and what their moves reach. May be given "
+                    "several times: the files are applied in order, every "
+                    "run starts from the partition the one before returned, "
+                    "and -o, --exact-modularity and --check-connected act "
+                    "on the last result")
     ap.add_argument("--exact-modularity", action="store_true",
                     help="after the run, print the exact modularity of the "
                     "returned partition (\"Final modularity\" is the "
@@ -333,66 +338,13 @@ def write_dist_graph_collect(path: str, dg: DistGraph, comm: Comm):
         print(f"Wrote generated graph to {path}")
 
 
-def main(argv=None) -> int:
-    args = build_parser().parse_args(argv)
-    comm = init_from_env(prefer=args.device)
-    validate(args, comm.world)
-    if args.diag_files:
-        # reference default: per-rank dat.out.<rank> diagnostic files
-        sys.stdout = open(f"dat.out.{comm.rank}", "w")
-
-    t0 = time.perf_counter()
-    try:
-        dg = _ingest(args, comm)
-    except FileNotFoundError as e:
-        sys.exit(f"Error opening graph file: {e.filename}")
-    t_ingest = time.perf_counter() - t0
-    ne_global = comm.allreduce_scalar(float(dg.ne))
-    if comm.rank == 0:
-        print(f"Graph: nv={dg.nv_global} ne(directed)={int(ne_global)} "
-              f"ranks={comm.world} device={comm.device.type} "
-              f"ingest={t_ingest:.3f}s")
-    if args.stats or args.just_process:
-        print_dist_stats(dg, comm)
-    if args.just_process:
-        return 0
-    gamma = 1.0 if args.resolution is None else args.resolution
-    if args.resolution is not None and comm.rank == 0:
-        print(f"Resolution: {gamma:g}")
-
-    if args.score_communities:
-        part_labels = _load_partition_slice(args.score_communities, args, dg)
-        pq = partition_quality(dg, part_labels, comm, backend=args.backend,
-                               resolution=gamma)
-        if comm.rank == 0:
-            print(f"Partition {args.score_communities}: "
-                  f"modularity={pq.modularity:.15g} "
-                  f"communities={pq.num_communities} "
-                  f"coverage={pq.coverage:.15g}")
-        if args.check_connected:
-            _print_connectivity(dg, part_labels, comm, args.backend)
-        return 0
-    init_labels = None
-    if args.init_communities:
-        init_labels = _load_partition_slice(args.init_communities, args, dg)
-    init_frontier = None
-    if args.update_edges:
-        # the ingested graph is the old one; rank 0 passes the whole batch,
-        # the other ranks an empty share
-        from .dynamic import EdgeBatch, affected_vertices, apply_edge_batch
-        batch = _load_edge_batch(args.update_edges, dg.nv_global)
-        n_ins, n_del = batch.ins_src.numel(), batch.del_src.numel()
-        share = batch if comm.rank == 0 else EdgeBatch.empty()
-        try:
-            dg = apply_edge_batch(dg, comm, share)
-        except ValueError as e:
-            sys.exit(f"{args.update_edges}: {e}")
-        init_frontier = affected_vertices(dg, comm, init_labels, share)
-        n_aff = int(comm.allreduce_scalar(float(init_frontier.sum())))
-        if comm.rank == 0:
-            print(f"Edge batch: inserted={n_ins} deleted={n_del} "
-                  f"affected={n_aff}")
-
+def _cluster(args, comm: Comm, cfg: LouvainConfig, dg: DistGraph,
+             init_labels, init_frontier, ne_global: float):
+    """One clustering run and its report lines: the optional degree
+    relabelling, the "Initial partition" line, louvain, and rank 0's summary.
+    Returns (result, the graph that was clustered, vo_inv, vo_gmap); the two
+    maps are None unless --vertex-order degree relabelled the graph."""
+    gamma = cfg.resolution
     vo_inv = None     # new local pos -> old local pos (inverse applied later)
     vo_gmap = None    # old gid -> new gid
     if args.vertex_order == "degree":
@@ -401,25 +353,6 @@ def main(argv=None) -> int:
         vo_inv = torch.empty_like(vo_order)
         vo_inv[vo_order] = torch.arange(vo_order.numel(),
                                         device=vo_order.device)
-
-    cfg = LouvainConfig(
-        threshold=args.threshold,
-        threshold_scaling=args.threshold_cycling,
-        one_phase=args.one_phase,
-        early_term=args.early_term,
-        et_delta=args.et_alpha,
-        coloring=args.coloring > 0,
-        ordering=args.ordering > 0,
-        max_colors=max(args.coloring, args.ordering) or 8,
-        backend=args.backend,
-        verbose=args.verbose,
-        connectivity=args.connectivity,
-        algorithm="leiden" if args.leiden else "louvain",
-        vcycle=args.vcycle,
-        resolution=gamma,
-    )
-    if args.max_phases:
-        cfg.max_phases = args.max_phases
 
     if init_labels is not None:
         if vo_inv is not None:
@@ -486,6 +419,113 @@ def main(argv=None) -> int:
                   f"device {hbm_gb:.2f} GB")
         else:
             print(f"Peak memory: host rss {rss_mb:.0f} MB")
+    return res, dg, vo_inv, vo_gmap
+
+
+def _input_order(labels: torch.Tensor, vo_inv, vo_gmap) -> torch.Tensor:
+    """Labels of a clustered graph in the INPUT vertex order and id space:
+    original local vertex v sits at relabelled position vo_inv[v]; label
+    values (new gids) map through the global inverse."""
+    if vo_inv is None:
+        return labels
+    labels = labels[vo_inv]
+    inv_gmap = torch.empty_like(vo_gmap)
+    inv_gmap[vo_gmap] = torch.arange(vo_gmap.numel(), device=vo_gmap.device)
+    return inv_gmap[labels]
+
+
+def main(argv=None) -> int:
+    args = build_parser().parse_args(argv)
+    comm = init_from_env(prefer=args.device)
+    validate(args, comm.world)
+    if args.diag_files:
+        # reference default: per-rank dat.out.<rank> diagnostic files
+        sys.stdout = open(f"dat.out.{comm.rank}", "w")
+
+    t0 = time.perf_counter()
+    try:
+        dg = _ingest(args, comm)
+    except FileNotFoundError as e:
+        sys.exit(f"Error opening graph file: {e.filename}")
+    t_ingest = time.perf_counter() - t0
+    ne_global = comm.allreduce_scalar(float(dg.ne))
+    if comm.rank == 0:
+        print(f"Graph: nv={dg.nv_global} ne(directed)={int(ne_global)} "
+              f"ranks={comm.world} device={comm.device.type} "
+              f"ingest={t_ingest:.3f}s")
+    if args.stats or args.just_process:
+        print_dist_stats(dg, comm)
+    if args.just_process:
+        return 0
+    gamma = 1.0 if args.resolution is None else args.resolution
+    if args.resolution is not None and comm.rank == 0:
+        print(f"Resolution: {gamma:g}")
+
+    if args.score_communities:
+        part_labels = _load_partition_slice(args.score_communities, args, dg)
+        pq = partition_quality(dg, part_labels, comm, backend=args.backend,
+                               resolution=gamma)
+        if comm.rank == 0:
+            print(f"Partition {args.score_communities}: "
+                  f"modularity={pq.modularity:.15g} "
+                  f"communities={pq.num_communities} "
+                  f"coverage={pq.coverage:.15g}")
+        if args.check_connected:
+            _print_connectivity(dg, part_labels, comm, args.backend)
+        return 0
+    init_labels = None
+    if args.init_communities:
+        init_labels = _load_partition_slice(args.init_communities, args, dg)
+    cfg = LouvainConfig(
+        threshold=args.threshold,
+        threshold_scaling=args.threshold_cycling,
+        one_phase=args.one_phase,
+        early_term=args.early_term,
+        et_delta=args.et_alpha,
+        coloring=args.coloring > 0,
+        ordering=args.ordering > 0,
+        max_colors=max(args.coloring, args.ordering) or 8,
+        backend=args.backend,
+        verbose=args.verbose,
+        connectivity=args.connectivity,
+        algorithm="leiden" if args.leiden else "louvain",
+        vcycle=args.vcycle,
+        resolution=gamma,
+    )
+    if args.max_phases:
+        cfg.max_phases = args.max_phases
+
+    # every update file is read before any work is done. Rank 0 passes the
+    # whole batch, the other ranks an empty share
+    batches = [(path, _load_edge_batch(path, dg.nv_global))
+               for path in args.update_edges]
+    runs = batches or [None]
+    for k, item in enumerate(runs, 1):
+        init_frontier = None
+        if item is not None:
+            # the graph so far is the old one
+            from .dynamic import (EdgeBatch, affected_vertices,
+                                  apply_edge_batch)
+            path, batch = item
+            if len(runs) > 1 and comm.rank == 0:
+                print(f"Batch {k}/{len(runs)}: {path}")
+            n_ins, n_del = batch.ins_src.numel(), batch.del_src.numel()
+            share = batch if comm.rank == 0 else EdgeBatch.empty()
+            try:
+                dg = apply_edge_batch(dg, comm, share)
+            except ValueError as e:
+                sys.exit(f"{path}: {e}")
+            init_frontier = affected_vertices(dg, comm, init_labels, share)
+            n_aff = int(comm.allreduce_scalar(float(init_frontier.sum())))
+            if comm.rank == 0:
+                print(f"Edge batch: inserted={n_ins} deleted={n_del} "
+                      f"affected={n_aff}")
+        res, run_dg, vo_inv, vo_gmap = _cluster(
+            args, comm, cfg, dg, init_labels, init_frontier, ne_global)
+        if k < len(runs):
+            # the next batch starts from this result, in input vertex order
+            init_labels = _input_order(res.communities, vo_inv, vo_gmap)
+    dg = run_dg  # what the last run clustered
 
     if args.exact_modularity:
         # res.communities labels the graph that was clustered (after
@@ -501,16 +541,9 @@ def main(argv=None) -> int:
 
     builtin_truth = getattr(args, "_lfr_truth", None)
     if args.output or args.ground_truth or builtin_truth is not None:
-        final_comm = res.communities
-        if vo_inv is not None:
-            # map back to the INPUT vertex order: original local vertex v sits
-            # at relabeled position vo_inv[v]; label values (new gids) map
-            # through the global inverse so dumps match the input id space
-            final_comm = final_comm[vo_inv]
-            inv_gmap = torch.empty_like(vo_gmap)
-            inv_gmap[vo_gmap] = torch.arange(vo_gmap.numel(),
-                                             device=vo_gmap.device)
-            final_comm = inv_gmap[final_comm]
+        # map back to the INPUT vertex order so dumps match the input id
+        # space
+        final_comm = _input_order(res.communities, vo_inv, vo_gmap)
         # gather final communities to root in vertex order
         allc = comm.gather_cat(final_comm.to(comm.device), root=0)
         if comm.rank == 0:

@@ -28,13 +28,18 @@ later phases are ordinary phases on the coarsened graph.
 Edge batches (`EdgeBatch`, `apply_edge_batch`) hold global ids, each
 undirected edge once. In a multi-rank run every rank passes its own share of
 the batch; the batch is the union of the shares, and a rank's share may name
-any vertices.
+any vertices. A batch is routed to the owners of its sources and then applied
+to every rank's CSR on its own: on the GPU by ops.apply_batch, whose result,
+row order included, is the one of its twin apply_routed_batch_torch; on the
+CPU by a rebuild of the CSR. `update_stream` follows a sequence of batches,
+carrying graph and partition from one to the next.
 """
 
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass, field
-from typing import Callable, List, Optional
+from typing import Callable, List, Optional, Sequence
 
 import torch
 
@@ -412,6 +417,94 @@ def _route_by_owner(dg: DistGraph, comm: Comm, key: torch.Tensor, *cols):
     return tuple(out)
 
 
+def _route_batch(dg: DistGraph, comm: Comm, batch: EdgeBatch):
+    """Both directions of every change, each at the owner of its source:
+    (d_src, d_dst, i_src, i_dst, i_w), global ids, i_w in fp64."""
+    d_src, d_dst = _directed(batch.del_src, batch.del_dst)
+    d_src, d_dst = _route_by_owner(dg, comm, d_src, d_dst)
+    i_src, i_dst, i_w = _directed(batch.ins_src, batch.ins_dst,
+                                  batch.ins_w.to(torch.float64))
+    i_src, i_dst, i_w = _route_by_owner(dg, comm, i_src, i_dst, i_w)
+    return d_src, d_dst, i_src, i_dst, i_w
+
+
+def _stable_rows(g: Graph, base: int, nv_global: int, d_src, d_dst, i_src,
+                 i_dst, i_w):
+    """apply_routed_batch_torch without the raise: (Graph or None, absent)."""
+    nv, dev = g.nv, g.device
+    src = torch.repeat_interleave(torch.arange(nv, device=dev), g.degrees())
+    key = src * nv_global + g.tails
+    dkey = torch.unique((d_src - base) * nv_global + d_dst)
+    if dkey.numel() > 0 and not bool(torch.isin(dkey, key).all()):
+        return None, True
+    keep = ~torch.isin(key, dkey)
+    # old entries first, then the insertions: a stable sort by source leaves
+    # both in their order inside every row
+    rows = torch.cat([src[keep], i_src - base])
+    order = torch.argsort(rows, stable=True)
+    rowptr = torch.zeros(nv + 1, dtype=torch.int64, device=dev)
+    if rows.numel():
+        rowptr[1:] = torch.cumsum(torch.bincount(rows, minlength=nv), dim=0)
+    tails = torch.cat([g.tails[keep], i_dst])[order]
+    weights = torch.cat([g.weights[keep], i_w.to(g.weights.dtype)])[order]
+    return Graph(rowptr, tails, weights), False
+
+
+def apply_routed_batch_torch(g: Graph, base: int, nv_global: int,
+                             d_src: torch.Tensor, d_dst: torch.Tensor,
+                             i_src: torch.Tensor, i_dst: torch.Tensor,
+                             i_w: torch.Tensor) -> Graph:
+    """Twin of ops.apply_batch: the routed lists of one rank (directed,
+    global ids, every source owned by this rank) applied to its CSR `g`, with
+    the order inside a row fixed ("stable rows"):
+
+      - row v keeps its old entries whose (v, dst) is not in the deletion
+        set, in their old order;
+      - after them come the insertions with source v, in the order of the
+        routed list;
+      - weights are copied (cast to the graph's dtype), never added.
+
+    A deletion that matches no stored entry raises ValueError; `g` is never
+    modified. Works on any device; runs over all `ne` entries."""
+    out, absent = _stable_rows(g, base, nv_global, d_src, d_dst, i_src,
+                               i_dst, i_w)
+    if absent:
+        raise ValueError("edge batch deletes an edge the graph does not hold")
+    return out
+
+
+def _rebuild(g: Graph, base: int, nv_global: int, d_src, d_dst, i_src, i_dst,
+             i_w):
+    """The whole-graph rebuild through Graph.from_edge_tuples: (Graph or
+    None, absent). Row order is the builder's: sorted by dst on the CPU, open
+    on the device."""
+    nv, dev = g.nv, g.device
+    src = base + torch.repeat_interleave(
+        torch.arange(nv, device=dev), g.degrees())
+    key = src * nv_global + g.tails
+    dkey = torch.unique(d_src * nv_global + d_dst)
+    if dkey.numel() > 0 and not bool(torch.isin(dkey, key).all()):
+        return None, True
+    keep = ~torch.isin(key, dkey)
+    return Graph.from_edge_tuples(
+        nv, torch.cat([src[keep], i_src]),
+        torch.cat([g.tails[keep], i_dst]),
+        torch.cat([g.weights[keep], i_w.to(g.weights.dtype)]),
+        base=base), False
+
+
+def _batch_on_device(dev) -> bool:
+    """Whether apply_edge_batch takes the HIP path (ops.apply_batch): the
+    graph is on the GPU, the extension is built and CUVITE_BATCH_DEVICE is
+    not 0 (read per call)."""
+    if dev.type != "cuda":
+        return False
+    if os.environ.get("CUVITE_BATCH_DEVICE", "1") in ("0", "off"):
+        return False
+    from . import ops
+    return ops.available()
+
+
 def apply_edge_batch(dg: DistGraph, comm: Comm,
                      batch: EdgeBatch) -> DistGraph:
     """The graph after the batch: same vertex set and partition. Collective;
@@ -420,35 +513,28 @@ def apply_edge_batch(dg: DistGraph, comm: Comm,
     rows; a deletion that matches nothing raises ValueError on every rank. An
     insertion adds (u, v, w) and (v, u, w), or a self-loop once; a pair that
     is already present becomes a parallel edge. Deletions apply to the old
-    graph, insertions come after. The CSR is rebuilt through
-    Graph.from_edge_tuples."""
+    graph, insertions come after. The input graph is not modified.
+
+    On the GPU the routed lists are applied by ops.apply_batch: work on the
+    touched rows plus one copy of the CSR, rows in the stable order of
+    apply_routed_batch_torch. On the CPU, and with CUVITE_BATCH_DEVICE=0, the
+    CSR is rebuilt through Graph.from_edge_tuples."""
     if dg.g._ne_released >= 0:
         raise RuntimeError("tails released: apply edge batches before "
                            "Graph.release_tails()")
     _check_batch(dg, comm, batch)
     dev = dg.g.device
     batch = batch.to(dev)
-    base, nv, nvg = dg.base, dg.nv, dg.nv_global
-    W = dg.g.weights.dtype
-
-    d_src, d_dst = _directed(batch.del_src, batch.del_dst)
-    d_src, d_dst = _route_by_owner(dg, comm, d_src, d_dst)
-    i_src, i_dst, i_w = _directed(batch.ins_src, batch.ins_dst,
-                                  batch.ins_w.to(torch.float64))
-    i_src, i_dst, i_w = _route_by_owner(dg, comm, i_src, i_dst, i_w)
-
-    src = base + torch.repeat_interleave(
-        torch.arange(nv, device=dev), dg.g.degrees())
-    key = src * nvg + dg.g.tails
-    dkey = torch.unique(d_src * nvg + d_dst)
-    absent = dkey.numel() > 0 and not bool(torch.isin(dkey, key).all())
+    routed = _route_batch(dg, comm, batch)
+    if _batch_on_device(dev):
+        from . import ops
+        out = ops.apply_batch(dg.g.rowptr, dg.g.tails, dg.g.weights, dg.base,
+                              dg.nv_global, *routed)
+        g, absent = (None, True) if out is None else (Graph(*out), False)
+    else:
+        g, absent = _rebuild(dg.g, dg.base, dg.nv_global, *routed)
     if comm.allreduce_scalar(1.0 if absent else 0.0) > 0.0:
         raise ValueError("edge batch deletes an edge the graph does not hold")
-    keep = ~torch.isin(key, dkey)
-    g = Graph.from_edge_tuples(
-        nv, torch.cat([src[keep], i_src]),
-        torch.cat([dg.g.tails[keep], i_dst]),
-        torch.cat([dg.g.weights[keep], i_w.to(W)]), base=base)
     return DistGraph(g, dg.partition, dg.rank)
 
 
@@ -484,3 +570,68 @@ def affected_vertices(dg_new: DistGraph, comm: Comm, prev: torch.Tensor,
     mask = torch.zeros(nv, dtype=torch.bool, device=dev)
     mask[mine - base] = True
     return mask
+
+
+# ---------------------------------------------------------------------------
+# a stream of batches
+# ---------------------------------------------------------------------------
+
+@dataclass
+class StreamStep:
+    """One batch of update_stream."""
+
+    inserted: int       # undirected insertions of the batch, all ranks
+    deleted: int        # undirected deletions listed in the batch, all ranks
+    affected: int       # size of the first frontier, all ranks
+    result: object      # the LouvainResult of the run after the batch
+
+
+class StreamError(ValueError):
+    """A batch of update_stream was refused. `steps`: the StreamSteps
+    finished before it, still valid; `dg`: the graph they reached."""
+
+    def __init__(self, message: str, steps: List[StreamStep], dg: DistGraph):
+        super().__init__(message)
+        self.steps = steps
+        self.dg = dg
+
+
+_STREAM_REJECTS = ("coloring", "ordering", "early_term", "threshold_scaling")
+
+
+def update_stream(dg: DistGraph, comm: Comm, cfg, prev: torch.Tensor,
+                  batches: Sequence[EdgeBatch]):
+    """Follow a stream of edge batches: for every batch in order apply it
+    (apply_edge_batch), mark the affected vertices under the current labels
+    (affected_vertices) and run louvain from those labels with that frontier;
+    the run's communities are the labels the next batch starts from.
+    Collective: every rank passes its own share of each batch and its slice
+    `prev` of the partition of `dg`. Returns (graph after the last batch,
+    [StreamStep per batch]).
+
+    Coloring, ordering, early termination and threshold scaling are rejected
+    on every rank before any collective, as louvain(init_frontier=...) does.
+    A bad batch raises StreamError (a ValueError) at its step, on every
+    rank; it carries the finished steps and the graph they reached."""
+    for flag in _STREAM_REJECTS:
+        if getattr(cfg, flag):
+            raise ValueError(f"update_stream cannot be combined with {flag}")
+    from .louvain import louvain
+    labels = prev
+    steps: List[StreamStep] = []
+    for batch in batches:
+        try:
+            new = apply_edge_batch(dg, comm, batch)
+            mask = affected_vertices(new, comm, labels, batch)
+        except ValueError as e:
+            raise StreamError(str(e), steps, dg) from e
+        dg = new
+        counts = [float(batch.ins_src.numel()), float(batch.del_src.numel()),
+                  float(mask.sum())]
+        if comm.world > 1:
+            counts = [comm.allreduce_scalar(c) for c in counts]
+        res = louvain(dg, comm, cfg, init_labels=labels, init_frontier=mask)
+        steps.append(StreamStep(int(counts[0]), int(counts[1]),
+                                int(counts[2]), res))
+        labels = res.communities
+    return dg, steps

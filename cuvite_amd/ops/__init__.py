@@ -635,6 +635,76 @@ def frontier_move(inp, active: torch.Tensor, cw_prev: torch.Tensor,
         lambda: _hub_moves_sorted(inp, hubs64, hdeg), hub_mask=hub_mask)
 
 
+def batch_span() -> int:
+    """Touched entries per wave span of the edge-batch kernels (tests build
+    their shapes around it)."""
+    return int(_require().batch_span())
+
+
+def apply_batch(rowptr: torch.Tensor, tails: torch.Tensor,
+                weights: torch.Tensor, base: int, nv_global: int,
+                d_src: torch.Tensor, d_dst: torch.Tensor,
+                i_src: torch.Tensor, i_dst: torch.Tensor, i_w: torch.Tensor):
+    """The CSR (rowptr, tails, weights) of one rank after its routed lists
+    (directed, global ids, every source in [base, base + nv)): deletions
+    (d_src, d_dst), then insertions (i_src, i_dst, i_w). Rows come out in the
+    stable order of the twin, dynamic.apply_routed_batch_torch, bit for bit.
+    Returns (new_rowptr, new_tails, new_weights), fresh tensors, or None if a
+    deletion matches no stored entry; the inputs are never modified.
+
+    Host side: torch ops over batch-sized and nv-sized tensors only (sort and
+    deduplicate the lists, the touched rows and their slices, the new
+    degrees). Device: mark / copy / compact / insert kernels
+    (louvain_kernels.hip). A constant number of host syncs: two explicit
+    ones, the touched rows' entry count and then "any deletion unmatched"
+    with the new edge count, plus those inside the two torch.unique calls,
+    which size their outputs.
+    Beside the new CSR it allocates one byte per touched entry, int64 per
+    span and per touched row, and O(nv)."""
+    ext = _require()
+    dev = rowptr.device
+    nv = rowptr.numel() - 1
+    if d_src.numel() == 0 and i_src.numel() == 0:
+        return rowptr.clone(), tails.clone(), weights.clone()
+    i64 = dict(dtype=torch.int64, device=dev)
+    dkey = torch.unique((d_src - base) * nv_global + d_dst)  # (row, dst) order
+    drow = torch.div(dkey, nv_global, rounding_mode="floor")
+    ddst = (dkey - drow * nv_global).contiguous()
+    irow = i_src - base
+    order = torch.argsort(irow, stable=True)
+    irow = irow[order]
+    idst = i_dst[order].contiguous()
+    iw = i_w[order].to(weights.dtype).contiguous()
+    t_rows = torch.unique(torch.cat([drow, irow]))
+    nt = t_rows.numel()
+    edges = torch.cat([t_rows, torch.full((1,), nv, **i64)])
+    d_offs = torch.searchsorted(drow, edges).contiguous()
+    i_offs = torch.searchsorted(irow, edges).contiguous()
+    t_offs = torch.zeros(nt + 1, **i64)
+    t_offs[1:] = torch.cumsum(rowptr[t_rows + 1] - rowptr[t_rows], dim=0)
+    n_touched = int(t_offs[-1])  # host sync: sizes the keep flags
+    keep, span_cnt, row_kept, matched = ext.batch_mark(
+        rowptr, tails, t_rows, t_offs, n_touched, d_offs, ddst)
+    deg = rowptr[1:] - rowptr[:-1]
+    deg[t_rows] = row_kept + (i_offs[1:] - i_offs[:-1])
+    new_rowptr = torch.zeros(nv + 1, **i64)
+    new_rowptr[1:] = torch.cumsum(deg, dim=0)
+    del deg
+    touched = torch.zeros(nv, dtype=torch.uint8, device=dev)
+    touched[t_rows] = 1
+    absent, new_ne = torch.stack([
+        (matched == 0).any().to(torch.int64), new_rowptr[-1]]).tolist()
+    if absent:
+        return None
+    span_offs = torch.cumsum(span_cnt, dim=0) - span_cnt
+    kept_offs = torch.cumsum(row_kept, dim=0) - row_kept
+    new_tails, new_weights = ext.batch_write(
+        rowptr, tails, weights, t_rows, t_offs, n_touched, keep, span_offs,
+        kept_offs, row_kept, touched, new_rowptr, int(new_ne), i_offs, idst,
+        iw)
+    return new_rowptr, new_tails, new_weights
+
+
 def modularity_parts(cluster_weight: torch.Tensor,
                      local_comm_degree: torch.Tensor) -> torch.Tensor:
     """HIP reduction of (sum cluster_weight, sum degree^2) in fp64."""

@@ -793,9 +793,181 @@ std::vector<at::Tensor> frontier_compact(at::Tensor active, at::Tensor cls) {
   return {lists, counts};
 }
 
+void check_i64(const at::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous(), name,
+              " must be a contiguous GPU tensor");
+  TORCH_CHECK(t.scalar_type() == at::kLong, name, " must be int64");
+}
+
+// The part of the batch arguments that both bindings fill: the old CSR and
+// the touched rows.
+cuvite::BatchRows batch_rows(const at::Tensor& rowptr, const at::Tensor& tails,
+                             const at::Tensor& t_rows,
+                             const at::Tensor& t_offs, int64_t n_touched) {
+  check_i64(rowptr, "rowptr");
+  check_i64(tails, "tails");
+  check_i64(t_rows, "t_rows");
+  check_i64(t_offs, "t_offs");
+  TORCH_CHECK(rowptr.numel() >= 1, "rowptr must have nv + 1 entries");
+  TORCH_CHECK(t_offs.numel() == t_rows.numel() + 1,
+              "t_offs must have one entry more than t_rows");
+  TORCH_CHECK(n_touched >= 0 && n_touched <= tails.numel(),
+              "n_touched must lie in [0, ne]");
+  cuvite::BatchRows r{};
+  r.rowptr = rowptr.data_ptr<int64_t>();
+  r.tails = tails.data_ptr<int64_t>();
+  r.nv = rowptr.numel() - 1;
+  r.ne = tails.numel();
+  r.t_rows = t_rows.data_ptr<int64_t>();
+  r.t_offs = t_offs.data_ptr<int64_t>();
+  r.nt = t_rows.numel();
+  r.n_touched = n_touched;
+  return r;
+}
+
+// Edge batch, first half (see batch_mark_kernel). t_rows: the touched local
+// rows, ascending, each in [0, nv); t_offs: prefix sums of their old degrees,
+// n_touched = t_offs[nt] as the host knows it; d_offs / d_dst: per-row slices
+// of the deduplicated deletions, tails ascending inside a row. Returns (keep
+// uint8 [n_touched], span_cnt int64 [spans], row_kept int64 [nt], matched
+// uint8 [nd]). No host sync.
+std::vector<at::Tensor> batch_mark(at::Tensor rowptr, at::Tensor tails,
+                                   at::Tensor t_rows, at::Tensor t_offs,
+                                   int64_t n_touched, at::Tensor d_offs,
+                                   at::Tensor d_dst) {
+  cuvite::BatchMarkArgs a{};
+  a.rows = batch_rows(rowptr, tails, t_rows, t_offs, n_touched);
+  check_i64(d_offs, "d_offs");
+  check_i64(d_dst, "d_dst");
+  TORCH_CHECK(d_offs.numel() == a.rows.nt + 1,
+              "d_offs must have one entry more than t_rows");
+  auto u8 = rowptr.options().dtype(at::kByte);
+  auto keep = at::empty({n_touched}, u8);
+  auto span_cnt = at::zeros({cuvite::batch_spans(n_touched)},
+                            rowptr.options());
+  auto row_kept = at::zeros({a.rows.nt}, rowptr.options());
+  auto matched = at::zeros({d_dst.numel()}, u8);
+  a.d_offs = d_offs.data_ptr<int64_t>();
+  a.d_dst = d_dst.data_ptr<int64_t>();
+  a.nd = d_dst.numel();
+  a.d_matched = matched.data_ptr<uint8_t>();
+  a.keep = keep.data_ptr<uint8_t>();
+  a.span_cnt = span_cnt.data_ptr<int64_t>();
+  a.row_kept = row_kept.data_ptr<int64_t>();
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  cuvite::launch_batch_mark(a, stream);
+  C10_HIP_CHECK(hipGetLastError());
+  return {keep, span_cnt, row_kept, matched};
+}
+
+template <typename W>
+std::vector<at::Tensor> batch_write_impl(
+    const at::Tensor& rowptr, const at::Tensor& tails,
+    const at::Tensor& weights, const at::Tensor& t_rows,
+    const at::Tensor& t_offs, int64_t n_touched, const at::Tensor& keep,
+    const at::Tensor& span_offs, const at::Tensor& kept_offs,
+    const at::Tensor& row_kept, const at::Tensor& touched,
+    const at::Tensor& new_rowptr, int64_t new_ne, const at::Tensor& i_offs,
+    const at::Tensor& i_dst, const at::Tensor& i_w) {
+  cuvite::BatchWriteArgs<W> a{};
+  a.rows = batch_rows(rowptr, tails, t_rows, t_offs, n_touched);
+  auto new_tails = at::empty({new_ne}, tails.options());
+  auto new_weights = at::empty({new_ne}, weights.options());
+  a.weights = weights.data_ptr<W>();
+  a.keep = keep.data_ptr<uint8_t>();
+  a.row_kept = row_kept.data_ptr<int64_t>();
+  a.touched = touched.data_ptr<uint8_t>();
+  a.span_offs = span_offs.data_ptr<int64_t>();
+  a.kept_offs = kept_offs.data_ptr<int64_t>();
+  a.new_rowptr = new_rowptr.data_ptr<int64_t>();
+  a.new_ne = new_ne;
+  a.new_tails = new_tails.data_ptr<int64_t>();
+  a.new_weights = new_weights.data_ptr<W>();
+  a.i_offs = i_offs.data_ptr<int64_t>();
+  a.i_dst = i_dst.data_ptr<int64_t>();
+  a.i_w = i_w.data_ptr<W>();
+  a.ni = i_dst.numel();
+  auto stream = at::hip::getCurrentHIPStream().stream();
+  cuvite::launch_batch_copy(a, stream);
+  cuvite::launch_batch_compact(a, stream);
+  C10_HIP_CHECK(hipGetLastError());
+  return {new_tails, new_weights};
+}
+
+// Edge batch, second half (batch_copy_kernel, batch_compact_kernel,
+// batch_insert_kernel): fills the new CSR's tails and weights. keep /
+// row_kept: batch_mark's results; span_offs / kept_offs: exclusive scans of
+// its span_cnt / row_kept; touched: uint8 [nv], 1 for every row of t_rows;
+// new_rowptr / new_ne: the new CSR's offsets and its edge count as the host
+// knows it; i_offs / i_dst / i_w: per-row slices of the insertions in list
+// order. Returns (new_tails int64 [new_ne], new_weights [new_ne]).
+std::vector<at::Tensor> batch_write(
+    at::Tensor rowptr, at::Tensor tails, at::Tensor weights, at::Tensor t_rows,
+    at::Tensor t_offs, int64_t n_touched, at::Tensor keep,
+    at::Tensor span_offs, at::Tensor kept_offs, at::Tensor row_kept,
+    at::Tensor touched, at::Tensor new_rowptr, int64_t new_ne,
+    at::Tensor i_offs, at::Tensor i_dst, at::Tensor i_w) {
+  CHECK_INPUT(weights);
+  CHECK_INPUT(keep);
+  CHECK_INPUT(touched);
+  CHECK_INPUT(i_w);
+  check_i64(span_offs, "span_offs");
+  check_i64(kept_offs, "kept_offs");
+  check_i64(row_kept, "row_kept");
+  check_i64(new_rowptr, "new_rowptr");
+  check_i64(i_offs, "i_offs");
+  check_i64(i_dst, "i_dst");
+  TORCH_CHECK(keep.scalar_type() == at::kByte &&
+              touched.scalar_type() == at::kByte,
+              "keep / touched must be uint8");
+  const int64_t nv = rowptr.numel() - 1;
+  const int64_t nt = t_rows.numel();
+  TORCH_CHECK(weights.numel() == tails.numel(), "tails / weights mismatch");
+  TORCH_CHECK(keep.numel() == n_touched, "keep must have n_touched entries");
+  TORCH_CHECK(span_offs.numel() == cuvite::batch_spans(n_touched),
+              "span_offs must have one entry per span");
+  TORCH_CHECK(kept_offs.numel() == nt && row_kept.numel() == nt &&
+              i_offs.numel() == nt + 1,
+              "kept_offs / row_kept / i_offs do not match t_rows");
+  TORCH_CHECK(touched.numel() == nv && new_rowptr.numel() == nv + 1,
+              "touched / new_rowptr do not match rowptr");
+  TORCH_CHECK(new_ne >= 0, "new_ne must not be negative");
+  TORCH_CHECK(i_w.numel() == i_dst.numel() &&
+              i_w.scalar_type() == weights.scalar_type(),
+              "i_w must match i_dst and the weight dtype");
+  if (weights.scalar_type() == at::kFloat)
+    return batch_write_impl<float>(rowptr, tails, weights, t_rows, t_offs,
+                                   n_touched, keep, span_offs, kept_offs,
+                                   row_kept, touched, new_rowptr, new_ne,
+                                   i_offs, i_dst, i_w);
+  TORCH_CHECK(weights.scalar_type() == at::kDouble,
+              "weights must be fp32 or fp64");
+  return batch_write_impl<double>(rowptr, tails, weights, t_rows, t_offs,
+                                  n_touched, keep, span_offs, kept_offs,
+                                  row_kept, touched, new_rowptr, new_ne,
+                                  i_offs, i_dst, i_w);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("batch_mark", &batch_mark,
+        "edge batch: keep flags, kept counts and matched deletions over the "
+        "touched rows (HIP); returns (keep, span_cnt, row_kept, matched)",
+        py::arg("rowptr"), py::arg("tails"), py::arg("t_rows"),
+        py::arg("t_offs"), py::arg("n_touched"), py::arg("d_offs"),
+        py::arg("d_dst"));
+  m.def("batch_write", &batch_write,
+        "edge batch: the new CSR's tails and weights, untouched rows copied, "
+        "touched rows compacted and appended to (HIP)",
+        py::arg("rowptr"), py::arg("tails"), py::arg("weights"),
+        py::arg("t_rows"), py::arg("t_offs"), py::arg("n_touched"),
+        py::arg("keep"), py::arg("span_offs"), py::arg("kept_offs"),
+        py::arg("row_kept"), py::arg("touched"), py::arg("new_rowptr"),
+        py::arg("new_ne"), py::arg("i_offs"), py::arg("i_dst"),
+        py::arg("i_w"));
+  m.def("batch_span", &cuvite::batch_span,
+        "touched entries per wave span of the edge-batch kernels");
   m.def("local_move_bucketed", &local_move,
         "Louvain local-move iteration (HIP, degree-class routed)",
         py::arg("rowptr"), py::arg("tails"), py::arg("weights"),

@@ -175,6 +175,63 @@ void launch_frontier_compact(const uint8_t* active, const uint8_t* cls,
 int frontier_classes();
 int64_t frontier_units(int64_t nv);
 
+// Arguments of the edge-batch kernels (batch_mark_kernel, batch_copy_kernel,
+// batch_compact_kernel, batch_insert_kernel). BatchRows: the old CSR with
+// global int64 tails and the nt touched rows, whose old entries form one
+// concatenated edge space of t_offs[nt] = n_touched entries.
+struct BatchRows {
+  const int64_t* rowptr;     // int64 [nv + 1]: old CSR
+  const int64_t* tails;      // int64 [ne]: global ids
+  int64_t nv, ne;
+  const int64_t* t_rows;     // int64 [nt]: touched local rows, ascending
+  const int64_t* t_offs;     // int64 [nt + 1]: prefix sums of their degrees
+  int64_t nt, n_touched;
+};
+
+// Mark: the touched rows' slices of the sorted deletion list and what the
+// pass stores. No weights are read.
+struct BatchMarkArgs {
+  BatchRows rows;
+  const int64_t* d_offs;     // int64 [nt + 1]: deletion slice of each row
+  const int64_t* d_dst;      // int64 [nd]: tails to delete, ascending per row
+  int64_t nd;
+  uint8_t* d_matched;        // uint8 [nd]: 1 is stored where an entry matched
+  uint8_t* keep;             // uint8 [n_touched]: 1 = the entry stays
+  int64_t* span_cnt;         // int64 [batch_spans(n_touched)]: kept per span
+  int64_t* row_kept;         // int64 [nt]: kept per row; zeroed by the caller
+};
+
+// Copy, compact and insert: mark's results, their scans and the new CSR.
+template <typename W>
+struct BatchWriteArgs {
+  BatchRows rows;
+  const W* weights;          // W [ne]
+  const uint8_t* keep;       // uint8 [n_touched]
+  const int64_t* row_kept;   // int64 [nt]
+  const uint8_t* touched;    // uint8 [nv]: 1 for a touched row
+  const int64_t* span_offs;  // int64 [spans]: exclusive scan of span_cnt
+  const int64_t* kept_offs;  // int64 [nt]: exclusive scan of row_kept
+  const int64_t* new_rowptr; // int64 [nv + 1]
+  int64_t new_ne;
+  int64_t* new_tails;        // int64 [new_ne]
+  W* new_weights;            // W [new_ne]
+  const int64_t* i_offs;     // int64 [nt + 1]: insertion slice of each row
+  const int64_t* i_dst;      // int64 [ni]: inserted tails, list order per row
+  const W* i_w;              // W [ni]
+  int64_t ni;
+};
+
+// Keep flags, per-span and per-row kept counts, matched deletions.
+void launch_batch_mark(const BatchMarkArgs& args, hipStream_t stream);
+// Untouched rows, moved to their new offset.
+template <typename W>
+void launch_batch_copy(const BatchWriteArgs<W>& args, hipStream_t stream);
+// Touched rows: kept entries in their old order, then the insertions.
+template <typename W>
+void launch_batch_compact(const BatchWriteArgs<W>& args, hipStream_t stream);
+int batch_span();
+int64_t batch_spans(int64_t n_touched);
+
 // rocPRIM wrappers, two-phase: temp == nullptr only stores the scratch size
 // in *bytes, a second call with that much scratch at temp does the work.
 template <typename W>

@@ -1090,6 +1090,240 @@ __global__ __launch_bounds__(256) void frontier_compact_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// Edge batches (cuvite_amd/dynamic.py, apply_edge_batch): the new CSR after
+// a batch of deletions and insertions, rows in the stable order of
+// dynamic.apply_routed_batch_torch. A batch of k edges touches at most 2k
+// rows; every other row of the new CSR is the old row at another offset. The
+// host side sorts the (batch-sized) lists and hands over the nt touched rows,
+// each with its slice of the deletions (ascending tails, deduplicated) and of
+// the insertions (list order). The touched rows' old entries are concatenated
+// into one edge space of t_offs[nt] entries, cut into spans of BA_SPAN with
+// one wave each, exactly as frontier_expand_kernel cuts the changed rows: a
+// touched hub is spread over many waves.
+//
+// Mark     every lane binary-searches its entry's tail in its row's deletion
+//          slice and stores the keep flag; a hit stores 1 into the matched
+//          byte of that deletion (idempotent plain store). Kept counts: one
+//          per span from the ballots, one per row from the runs of equal rows
+//          in the ballots. A run that goes on into the next chunk is carried
+//          in registers, so a row is written once per span it meets: a plain
+//          store where the row lies inside the span, an integer atomic add
+//          into the zeroed array where spans cut it (integer addition: the
+//          order does not matter).
+// Copy     over ALL old entries in spans of BA_COPY_SPAN as
+//          intra_weight_kernel cuts them: an entry of an untouched row goes
+//          to new_rowptr[row] + (e - rowptr[row]); consecutive lanes read
+//          and write consecutive addresses. Entries of touched rows are
+//          skipped before they are loaded.
+// Compact  over the touched edge space again: a kept entry goes to its
+//          stable position, span offset (exclusive scan of the span counts)
+//          plus ballot prefix, rebased from the kept-entry space to the row's
+//          start in the new CSR. Positions come from counts only, no atomics.
+// Insert   entry j of the sorted insertion list goes behind its row's kept
+//          entries, at its index inside the row's slice.
+//
+// Every loop is bounded by its span, there is no wait between waves and no
+// float atomic; every store into the new CSR is bounds-checked.
+// ---------------------------------------------------------------------------
+
+constexpr int BA_SPAN = 1024;       // touched entries per wave (mark, compact)
+constexpr int BA_COPY_SPAN = 4096;  // old entries per wave (copy)
+
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void batch_mark_kernel(
+    const int64_t* __restrict__ rowptr, const int64_t* __restrict__ tails,
+    int64_t ne, const int64_t* __restrict__ t_rows,
+    const int64_t* __restrict__ t_offs, int64_t nt, int64_t total,
+    const int64_t* __restrict__ d_offs, const int64_t* __restrict__ d_dst,
+    int64_t nd, uint8_t* __restrict__ d_matched, uint8_t* __restrict__ keep,
+    int64_t* __restrict__ span_cnt, int64_t* __restrict__ row_kept) {
+  constexpr int WAVES = BLOCK / 64;
+  const int lane = threadIdx.x % 64;
+  const uint64_t from_lane = ~(((uint64_t)1 << lane) - 1);  // lanes >= lane
+  const int64_t nspan = (total + BA_SPAN - 1) / BA_SPAN;
+  const int64_t sstride = (int64_t)gridDim.x * WAVES;
+  for (int64_t s = (int64_t)blockIdx.x * WAVES + threadIdx.x / 64; s < nspan;
+       s += sstride) {
+    const int64_t s0 = s * BA_SPAN;
+    const int64_t s1 = (s0 + BA_SPAN < total) ? s0 + BA_SPAN : total;
+    int64_t rlo, rhi;
+    span_row_range(t_offs, nt, s0, s1, rlo, rhi);
+    int64_t kept_span = 0;
+    int64_t carry_row = -1;  // row whose run goes on from the last chunk
+    int64_t carry_cnt = 0;
+    for (int64_t c = s0; c < s1; c += 64) {  // wave-uniform bounds
+      const int64_t e = c + lane;
+      const bool valid = e < s1;
+      int64_t r = -1;
+      bool kp = false;
+      if (valid) {
+        r = row_of_edge(t_offs, rlo, rhi, e);
+        const int64_t idx = rowptr[t_rows[r]] + (e - t_offs[r]);
+        kp = true;
+        if (idx >= 0 && idx < ne) {
+          const int64_t t = tails[idx];
+          int64_t lo = d_offs[r];
+          int64_t end = d_offs[r + 1];
+          if (lo < 0) lo = 0;
+          if (end > nd) end = nd;
+          int64_t hi = end;
+          while (lo < hi) {  // first deletion of the row with d_dst >= t
+            const int64_t m = (lo + hi) >> 1;
+            if (d_dst[m] < t) lo = m + 1; else hi = m;
+          }
+          if (lo < end && d_dst[lo] == t) {
+            kp = false;
+            d_matched[lo] = 1;
+          }
+        }
+        keep[e] = kp ? 1 : 0;
+      }
+      const uint64_t keptm = __ballot(kp);
+      kept_span += __popcll(keptm);
+      // runs of equal rows are contiguous lanes; the first lane of a run
+      // counts the run's kept entries
+      const int64_t prev_r = __shfl_up(r, 1, 64);
+      const bool head = valid && (lane == 0 || prev_r != r);
+      const uint64_t heads = __ballot(head);  // lane 0 is valid: not empty
+      const uint64_t above = lane == 63 ? 0 : heads & (from_lane << 1);
+      const int nh = above ? __ffsll((unsigned long long)above) - 1 : 64;
+      const uint64_t upto = nh == 64 ? ~(uint64_t)0 : ((uint64_t)1 << nh) - 1;
+      int64_t cnt = __popcll(keptm & upto & from_lane);
+      if (head && r == carry_row) cnt += carry_cnt;
+      const int64_t last_valid = (c + 64 < s1 ? c + 64 : s1) - 1;
+      bool emit = false, carry = false;
+      if (head) {
+        if (nh < 64) emit = true;  // the run ends inside the chunk
+        else if (t_offs[r + 1] - 1 <= last_valid || last_valid == s1 - 1)
+          emit = true;             // the row or the span ends with the chunk
+        else carry = true;
+      }
+      if (emit) {
+        if (t_offs[r] >= s0 && t_offs[r + 1] <= s1)
+          row_kept[r] = cnt;
+        else
+          atomicAdd((unsigned long long*)&row_kept[r],
+                    (unsigned long long)cnt);
+      }
+      const int last_head = 63 - __clzll((long long)heads);
+      const int carried = __shfl(carry ? 1 : 0, last_head, 64);
+      const int64_t c_cnt = __shfl(cnt, last_head, 64);
+      const int64_t c_row = __shfl(r, last_head, 64);
+      carry_row = carried ? c_row : -1;
+      carry_cnt = carried ? c_cnt : 0;
+      const int64_t last_row = __shfl(r, 63, 64);
+      if (last_row >= 0) rlo = last_row;
+    }
+    if (lane == 0) span_cnt[s] = kept_span;
+  }
+}
+
+template <typename W, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void batch_copy_kernel(
+    const int64_t* __restrict__ rowptr, const int64_t* __restrict__ tails,
+    const W* __restrict__ weights, int64_t nv, int64_t ne,
+    const uint8_t* __restrict__ touched,
+    const int64_t* __restrict__ new_rowptr, int64_t new_ne,
+    int64_t* __restrict__ new_tails, W* __restrict__ new_weights) {
+  constexpr int WAVES = BLOCK / 64;
+  const int lane = threadIdx.x % 64;
+  const int64_t nspan = (ne + BA_COPY_SPAN - 1) / BA_COPY_SPAN;
+  const int64_t sstride = (int64_t)gridDim.x * WAVES;
+  for (int64_t s = (int64_t)blockIdx.x * WAVES + threadIdx.x / 64; s < nspan;
+       s += sstride) {
+    const int64_t s0 = s * BA_COPY_SPAN;
+    const int64_t s1 = (s0 + BA_COPY_SPAN < ne) ? s0 + BA_COPY_SPAN : ne;
+    int64_t rlo, rhi;
+    span_row_range(rowptr, nv, s0, s1, rlo, rhi);
+    for (int64_t c = s0; c < s1; c += 64) {  // wave-uniform bounds
+      const int64_t e = c + lane;
+      int64_t r = -1;
+      if (e < s1) {
+        r = row_of_edge(rowptr, rlo, rhi, e);
+        if (!touched[r]) {  // a touched row's entries are not even read
+          const int64_t dst = new_rowptr[r] + (e - rowptr[r]);
+          if (dst >= 0 && dst < new_ne) {
+            new_tails[dst] = tails[e];
+            new_weights[dst] = weights[e];
+          }
+        }
+      }
+      const int64_t last_row = __shfl(r, 63, 64);
+      if (last_row >= 0) rlo = last_row;
+    }
+  }
+}
+
+template <typename W, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void batch_compact_kernel(
+    const int64_t* __restrict__ rowptr, const int64_t* __restrict__ tails,
+    const W* __restrict__ weights, int64_t ne,
+    const int64_t* __restrict__ t_rows, const int64_t* __restrict__ t_offs,
+    int64_t nt, int64_t total, const uint8_t* __restrict__ keep,
+    const int64_t* __restrict__ span_offs,
+    const int64_t* __restrict__ kept_offs,
+    const int64_t* __restrict__ new_rowptr, int64_t new_ne,
+    int64_t* __restrict__ new_tails, W* __restrict__ new_weights) {
+  constexpr int WAVES = BLOCK / 64;
+  const int lane = threadIdx.x % 64;
+  const uint64_t below = ((uint64_t)1 << lane) - 1;
+  const int64_t nspan = (total + BA_SPAN - 1) / BA_SPAN;
+  const int64_t sstride = (int64_t)gridDim.x * WAVES;
+  for (int64_t s = (int64_t)blockIdx.x * WAVES + threadIdx.x / 64; s < nspan;
+       s += sstride) {
+    const int64_t s0 = s * BA_SPAN;
+    const int64_t s1 = (s0 + BA_SPAN < total) ? s0 + BA_SPAN : total;
+    int64_t rlo, rhi;
+    span_row_range(t_offs, nt, s0, s1, rlo, rhi);
+    int64_t run = span_offs[s];  // kept entries before this span
+    for (int64_t c = s0; c < s1; c += 64) {  // wave-uniform bounds
+      const int64_t e = c + lane;
+      const bool valid = e < s1;
+      int64_t r = -1;
+      bool kp = false;
+      if (valid) {
+        r = row_of_edge(t_offs, rlo, rhi, e);
+        kp = keep[e] != 0;
+      }
+      const uint64_t m = __ballot(kp);
+      if (kp) {
+        const int64_t v = t_rows[r];
+        const int64_t idx = rowptr[v] + (e - t_offs[r]);
+        const int64_t rank = run + __popcll(m & below);
+        const int64_t dst = new_rowptr[v] + (rank - kept_offs[r]);
+        if (idx >= 0 && idx < ne && dst >= 0 && dst < new_ne) {
+          new_tails[dst] = tails[idx];
+          new_weights[dst] = weights[idx];
+        }
+      }
+      run += __popcll(m);
+      const int64_t last_row = __shfl(r, 63, 64);
+      if (last_row >= 0) rlo = last_row;
+    }
+  }
+}
+
+template <typename W>
+__global__ void batch_insert_kernel(
+    const int64_t* __restrict__ t_rows, int64_t nt,
+    const int64_t* __restrict__ i_offs, const int64_t* __restrict__ i_dst,
+    const W* __restrict__ i_w, int64_t ni,
+    const int64_t* __restrict__ row_kept,
+    const int64_t* __restrict__ new_rowptr, int64_t new_ne,
+    int64_t* __restrict__ new_tails, W* __restrict__ new_weights) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < ni;
+       j += stride) {
+    const int64_t r = row_of_edge(i_offs, 0, nt - 1, j);
+    const int64_t dst = new_rowptr[t_rows[r]] + row_kept[r] + (j - i_offs[r]);
+    if (dst >= 0 && dst < new_ne) {
+      new_tails[dst] = i_dst[j];
+      new_weights[dst] = i_w[j];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Hub candidate generation via rocPRIM: gather the neighbours' community
 // ids, then a per-hub segmented radix sort of those keys (only
 // ceil(log2 C) bits) with the edge weights as payload. The torch fallback
@@ -1741,6 +1975,61 @@ void launch_frontier_compact(const uint8_t* active, const uint8_t* cls,
                        0, stream, active, cls, nv, nunit, unit_cnt, unit_off,
                        class_base, lists);
 }
+
+int batch_span() { return BA_SPAN; }
+int64_t batch_spans(int64_t n_touched) {
+  return (n_touched + BA_SPAN - 1) / BA_SPAN;
+}
+
+void launch_batch_mark(const BatchMarkArgs& a, hipStream_t stream) {
+  const BatchRows& r = a.rows;
+  if (r.nt == 0 || r.n_touched <= 0) return;
+  constexpr int BLOCK = 256;
+  hipLaunchKernelGGL((batch_mark_kernel<BLOCK>),
+                     dim3(grid_for(batch_spans(r.n_touched) * 64, BLOCK)),
+                     dim3(BLOCK), 0, stream, r.rowptr, r.tails, r.ne, r.t_rows,
+                     r.t_offs, r.nt, r.n_touched, a.d_offs, a.d_dst, a.nd,
+                     a.d_matched, a.keep, a.span_cnt, a.row_kept);
+}
+
+template <typename W>
+void launch_batch_copy(const BatchWriteArgs<W>& a, hipStream_t stream) {
+  const BatchRows& r = a.rows;
+  if (r.nv == 0 || r.ne == 0) return;
+  constexpr int BLOCK = 256;
+  const int64_t nspan = (r.ne + BA_COPY_SPAN - 1) / BA_COPY_SPAN;
+  hipLaunchKernelGGL((batch_copy_kernel<W, BLOCK>),
+                     dim3(grid_for(nspan * 64, BLOCK)), dim3(BLOCK), 0, stream,
+                     r.rowptr, r.tails, a.weights, r.nv, r.ne, a.touched,
+                     a.new_rowptr, a.new_ne, a.new_tails, a.new_weights);
+}
+
+// Kept entries of the touched rows, then their insertions.
+template <typename W>
+void launch_batch_compact(const BatchWriteArgs<W>& a, hipStream_t stream) {
+  const BatchRows& r = a.rows;
+  constexpr int BLOCK = 256;
+  if (r.nt > 0 && r.n_touched > 0)
+    hipLaunchKernelGGL((batch_compact_kernel<W, BLOCK>),
+                       dim3(grid_for(batch_spans(r.n_touched) * 64, BLOCK)),
+                       dim3(BLOCK), 0, stream, r.rowptr, r.tails, a.weights,
+                       r.ne, r.t_rows, r.t_offs, r.nt, r.n_touched, a.keep,
+                       a.span_offs, a.kept_offs, a.new_rowptr, a.new_ne,
+                       a.new_tails, a.new_weights);
+  if (r.nt > 0 && a.ni > 0)
+    hipLaunchKernelGGL((batch_insert_kernel<W>), dim3(grid_for(a.ni, BLOCK)),
+                       dim3(BLOCK), 0, stream, r.t_rows, r.nt, a.i_offs,
+                       a.i_dst, a.i_w, a.ni, a.row_kept, a.new_rowptr,
+                       a.new_ne, a.new_tails, a.new_weights);
+}
+
+#define INSTANTIATE_BATCH(W)                                                  \
+  template void launch_batch_copy<W>(const BatchWriteArgs<W>&, hipStream_t); \
+  template void launch_batch_compact<W>(const BatchWriteArgs<W>&,            \
+                                        hipStream_t);
+INSTANTIATE_BATCH(float)
+INSTANTIATE_BATCH(double)
+#undef INSTANTIATE_BATCH
 
 // rocPRIM wrappers (two-phase: bytes query with temp==nullptr, then run).
 template <typename W>
